@@ -2,7 +2,9 @@
 """Flagship benchmark: Higgs-shape binary:logistic hist training on MI355X.
 
 Driver contract:
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line;
+--dump-outputs additionally saves the trained model as .npy arrays.
 For N > 1 the driver launches this under torch.distributed.run, one rank per
 GPU over RCCL. A "step" is one boosting iteration. Weak scaling: each GPU
 trains its own 12.5M x 28 row shard (N=8 -> the 100M x 28 BASELINE config;
@@ -62,15 +64,70 @@ def synth_shard(rows, features, device, seed):
     return X, y
 
 
+DUMP_SAMPLE_ROWS = 1 << 16
+DUMP_SAMPLE_SEED = 20240521
+
+
+def dump_outputs(out_dir, booster, X):
+    """Write what the timed training run returned to its caller — the
+    Booster — as DIR/<name>.npy, so two builds can be compared output for
+    output.
+
+    tree_*: every tree's node arrays, concatenated in boosting order
+    (tree_num_nodes gives the per-tree lengths; the trees of the last timed
+    step come last). Ids, bins and flags are stored as float64 (exact),
+    thresholds, leaf values, gains and hessian sums as float32.
+    margin_sample: the model's raw margin on a fixed, seeded sample of
+    DUMP_SAMPLE_ROWS training rows (float32) — comparable under a
+    tolerance even where two builds break a split tie differently.
+    A few MB in all at the default sizes.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    trees = [t.finalize() for t in booster.trees]
+    arrays = {"tree_num_nodes": np.asarray([t.num_nodes for t in trees], dtype=np.float64)}
+    for name, dtype in (
+        ("left", np.float64), ("right", np.float64), ("feature", np.float64),
+        ("split_bin", np.float64), ("default_left", np.float64),
+        ("threshold", np.float32), ("value", np.float32),
+        ("gain", np.float32), ("sum_hess", np.float32),
+    ):
+        arrays[f"tree_{name}"] = np.concatenate([np.asarray(getattr(t, name)) for t in trees]).astype(dtype)
+
+    g = torch.Generator(device="cpu")
+    g.manual_seed(DUMP_SAMPLE_SEED)
+    n = X.shape[0]
+    idx = torch.randperm(n, generator=g)[: min(n, DUMP_SAMPLE_ROWS)].sort().values
+    sample = X[idx.to(X.device)].cpu().numpy()
+    arrays["margin_sample_rows"] = idx.numpy().astype(np.float64)
+    arrays["margin_sample"] = np.asarray(
+        booster.predict(sample, output_margin=True), dtype=np.float32
+    )
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=100, help="timed boosting rounds")
+    ap.add_argument("--warmup", type=int, default=10, help="untimed rounds before the timed ones")
     ap.add_argument("--rows-per-gpu", type=int, default=ROWS_PER_GPU)
     ap.add_argument("--features", type=int, default=FEATURES)
     ap.add_argument("--max-depth", type=int, default=6)
     ap.add_argument("--max-bin", type=int, default=256)
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write the trained model's arrays and its margins on a "
+             "fixed row sample as DIR/<name>.npy (rank 0)",
+    )
+    ap.add_argument(
+        "--full", action="store_true",
+        help="also run the measurements and checks that the headline figure does not need. "
+             "This benchmark has none: everything else is measured by the scripts under "
+             "benchmarks/, so the option changes nothing here",
+    )
     args = ap.parse_args()
 
     use_gpu = torch.cuda.is_available()
@@ -106,7 +163,7 @@ def main():
         "eta": 0.3,
         "device": str(device),
     }
-    trainer.train(
+    booster = trainer.train(
         params,
         dtrain,
         num_boost_round=args.warmup + args.steps,
@@ -120,6 +177,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if use_gpu else "cpu")
         comm.allreduce_max_(t)
         elapsed = float(t[0])
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, booster, X)
 
     if rank == 0:
         rounds_per_sec = args.steps / elapsed

@@ -12,11 +12,8 @@ import os
 import numpy as np
 import pytest
 
-REF = "/root/reference/test/resources"
-
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(REF), reason="reference fixture tree not present"
-)
+# the subset of that corpus these tests read, stored with the suite
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_resources")
 
 
 # ---------------------------------------------------------------------------

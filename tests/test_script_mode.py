@@ -154,18 +154,65 @@ def test_script_mode_user_script_imports_xgboost(script_env, tmp_path, monkeypat
     assert len(bst.trees) == 5
 
 
-REF_ABALONE_SCRIPT = "/root/reference/test/resources/abalone/abalone_distributed.py"
+REF_MODULE_PATHS_SCRIPT = '''
+"""Customer script that knows only the reference container's module paths:
+`xgboost`, `sagemaker_containers.entry_point` and
+`sagemaker_xgboost_container.{distributed,data_utils}`."""
+import argparse
+import json
+import os
+
+import xgboost as xgb
+from sagemaker_containers import entry_point
+from sagemaker_xgboost_container import distributed
+from sagemaker_xgboost_container.data_utils import get_dmatrix
+
+HP_TYPES = {"max_depth": int, "eta": float, "gamma": int, "min_child_weight": int,
+            "subsample": float, "objective": str}
 
 
-@pytest.mark.skipif(not os.path.exists(REF_ABALONE_SCRIPT), reason="reference fixtures absent")
-def test_reference_abalone_script_runs_unmodified(script_env, tmp_path, monkeypatch):
-    """The reference's PUBLIC script-mode example (abalone_distributed.py)
-    must run VERBATIM: it imports `xgboost`, `sagemaker_containers.
-    entry_point` and `sagemaker_xgboost_container.{distributed,data_utils}`
-    — all satisfied by this container's compatibility packages."""
+def fit(params, dtrain, evals, num_boost_round, model_dir, is_master):
+    bst = xgb.train(params=params, dtrain=dtrain, evals=evals, num_boost_round=num_boost_round)
+    if is_master:
+        bst.save_model(os.path.join(model_dir, "xgboost-model"))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    for name, typ in HP_TYPES.items():
+        ap.add_argument("--" + name, type=typ)
+    ap.add_argument("--num_round", type=int)
+    opts, _ = ap.parse_known_args()
+
+    hosts = json.loads(os.environ["SM_HOSTS"])
+    dtrain = get_dmatrix(os.environ["SM_CHANNEL_TRAIN"], "libsvm")
+    dval = get_dmatrix(os.environ["SM_CHANNEL_VALIDATION"], "libsvm")
+    assert dtrain is not None and dval is not None
+    job = dict(
+        params={name: getattr(opts, name) for name in HP_TYPES},
+        dtrain=dtrain,
+        evals=[(dtrain, "train"), (dval, "validation")],
+        num_boost_round=opts.num_round,
+        model_dir=os.environ["SM_MODEL_DIR"],
+    )
+    if len(hosts) > 1:
+        entry_point._wait_hostname_resolution()
+        distributed.rabit_run(exec_fun=fit, args=job, include_in_training=True, hosts=hosts,
+                              current_host=os.environ["SM_CURRENT_HOST"], update_rabit_args=True)
+    else:
+        fit(is_master=True, **job)
+'''
+
+
+def test_reference_module_paths_script_runs(script_env, tmp_path, monkeypatch):
+    """A script-mode job written against the reference's PUBLIC module
+    paths (the shape of its abalone example: `xgboost`,
+    `sagemaker_containers.entry_point`,
+    `sagemaker_xgboost_container.{distributed,data_utils}`) must run as
+    is — all satisfied by this container's compatibility packages."""
     code_dir = tmp_path / "ref_code"
     code_dir.mkdir()
-    (code_dir / "abalone_distributed.py").write_text(open(REF_ABALONE_SCRIPT).read())
+    (code_dir / "abalone_distributed.py").write_text(REF_MODULE_PATHS_SCRIPT)
 
     # the reference example also reads a validation channel
     rng = np.random.default_rng(1)

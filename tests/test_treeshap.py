@@ -146,9 +146,10 @@ class TestExactTreeShap:
     def test_legacy_fixture_contribs(self):
         import os
 
-        path = "/root/reference/test/resources/models/saved_booster/xgboost-model"
-        if not os.path.exists(path):
-            pytest.skip("reference fixtures absent")
+        path = os.path.join(
+            os.path.dirname(os.path.abspath(__file__)),
+            "golden", "reference_resources", "models", "saved_booster", "xgboost-model",
+        )
         from sagemaker_xgboost_container_amd.models.booster import Booster
 
         b = Booster()

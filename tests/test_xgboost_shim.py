@@ -62,9 +62,10 @@ class TestCoreSurface:
     def test_plain_pickle_of_upstream_booster(self):
         # with the shim installed, xgboost.core.Booster resolves here and
         # the upstream pickle's handle-bytes state loads via __setstate__
-        path = "/root/reference/test/resources/models/pickled_model/xgboost-model"
-        if not os.path.exists(path):
-            pytest.skip("reference fixtures absent")
+        path = os.path.join(
+            os.path.dirname(os.path.abspath(__file__)),
+            "golden", "reference_resources", "models", "pickled_model", "xgboost-model",
+        )
         with open(path, "rb") as f:
             bst = pickle.load(f)
         assert isinstance(bst, xgb.Booster)
