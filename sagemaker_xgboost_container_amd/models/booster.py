@@ -184,16 +184,31 @@ class Booster:
         approx_contribs=False,
         training=False,
         ntree_limit=None,
+        pred_interactions=False,
     ):
-        """Predict for a DMatrix / ndarray. Returns numpy array."""
+        """Predict for a DMatrix / ndarray. Returns numpy array.
+
+        `pred_contribs` / `pred_interactions` / `pred_leaf` are mutually
+        exclusive; all three honour `iteration_range` / `ntree_limit`."""
+        if int(bool(pred_contribs)) + int(bool(pred_interactions)) + int(bool(pred_leaf)) > 1:
+            raise ValueError(
+                "only one of pred_contribs, pred_interactions and pred_leaf may be requested"
+            )
         X = self._as_tensor(data, validate_features)
         base_margin = getattr(data, "get_base_margin", lambda: None)()
         if ntree_limit:  # legacy alias: trees -> iterations
             iteration_range = (0, int(ntree_limit) // max(1, self._trees_per_round()))
         if pred_contribs:
-            return self._pred_contribs(X, approx=approx_contribs)
+            return self._pred_contribs(
+                X, approx=approx_contribs, iteration_range=iteration_range,
+                base_margin=base_margin,
+            )
+        if pred_interactions:
+            return self._pred_interactions(
+                X, iteration_range=iteration_range, base_margin=base_margin
+            )
         if pred_leaf:
-            return self._pred_leaf(X)
+            return self._pred_leaf(X, iteration_range=iteration_range)
         margin = self._margin(X, iteration_range, base_margin=base_margin)
         if output_margin:
             return margin.cpu().numpy()
@@ -256,15 +271,92 @@ class Booster:
             self._predict_cache = cache
         return cache["cpu_flat"]
 
-    def _pred_leaf(self, X):
-        """Leaf indices per (row, tree) — xgboost pred_leaf=True.
+    def _tree_range(self, iteration_range):
+        """[t_begin, t_end) of `iteration_range`; (0, 0) and None mean all
+        rounds, as in _margin."""
+        lo, hi = 0, self.num_boosted_rounds()
+        if iteration_range is not None and tuple(iteration_range) != (0, 0):
+            lo, hi = iteration_range
+            hi = min(hi, self.num_boosted_rounds()) if hi else self.num_boosted_rounds()
+        return self.iteration_indptr[lo], self.iteration_indptr[hi]
 
-        Vectorized: ONE parallel C++ traversal over the flat forest
-        (replaces the per-row Python loop; a 1M-row call is now
-        subsecond-scale instead of hours)."""
+    def _device_flat_forest(self, device, with_paths):
+        """hip flat forest on `device`, with the TreeSHAP path tables
+        attached when asked for. Forest and tables are cached under their
+        own keys, once per device."""
+        from ..ops import hip
+
+        cache = self._predict_cache or {}
+        self._predict_cache = cache
+        wd = self.weight_drop if any(w != 1.0 for w in self.weight_drop) else None
+        key = str(device)
+        if key not in cache:
+            cache[key] = hip.make_flat_forest(self.trees, self.tree_info, wd, device)
+        if not with_paths:
+            return cache[key]
+        pkey = "shap_paths:" + key
+        if pkey not in cache:
+            cache[pkey] = hip.make_shap_paths(self.trees, self.tree_info, wd, device)
+        return dict(cache[key], shap_paths=cache[pkey])
+
+    def _explain_on_device(self, X, t_begin, t_end, shap):
+        """The hip flat forest when the device kernels serve this request,
+        else None (host path). Device when X is on the GPU — so
+        predictor=cpu_predictor still forces the host — and, for TreeSHAP,
+        the longest path fits a wave and the phi slabs fit LDS. There is no
+        small-batch cut-off: the device arm wins at every measured size,
+        down to 1k rows (device explanations)."""
+        if X.device.type != "cuda" or not self.trees or t_end <= t_begin:
+            return None
+        hip = ops.backend_for(X.device)
+        if hip.NAME != "hip":
+            return None
+        flat = self._device_flat_forest(X.device, with_paths=shap)
+        if shap:
+            _, max_f, fits = hip.shap_limits(
+                flat["shap_paths"], self.n_outputs, X.shape[1], t_begin, t_end
+            )
+            if not fits or max_f >= X.shape[1]:
+                return None
+        return flat
+
+    def _expected_values(self, t_begin, t_end):
+        """Per-class TreeSHAP bias of trees [t_begin, t_end) (cached)."""
         from ..ops import torch_ref
 
-        return torch_ref.pred_leaf(self._cpu_flat_forest(), X.cpu()).numpy()
+        flat = self._cpu_flat_forest()
+        cache = self._predict_cache
+        key = ("expected_values", t_begin, t_end)
+        if key not in cache:
+            cache[key] = torch_ref.tree_expected_values(flat, self.n_outputs, t_begin, t_end)
+        return cache[key]
+
+    def _bias_rows(self, n, base_margin, device):
+        """(n, k) float64 starting margin: the DMatrix base_margin when
+        present, else the objective's transform of base_score."""
+        k = self.n_outputs
+        if base_margin is not None:
+            return torch.as_tensor(
+                np.asarray(base_margin), dtype=torch.float64, device=device
+            ).reshape(n, k)
+        base = float(self.objective().base_margin(self.base_score))
+        return torch.full((n, k), base, dtype=torch.float64, device=device)
+
+    def _pred_leaf(self, X, iteration_range=None):
+        """Leaf indices per (row, tree) — xgboost pred_leaf=True.
+
+        One thread per (row, tree) on the GPU (pred_leaf_kernel) when X is
+        there, else ONE parallel C++ traversal over the flat forest."""
+        from ..ops import torch_ref
+
+        if self.booster_type == "gblinear":
+            raise ValueError("pred_leaf is not defined for the gblinear booster")
+        t_begin, t_end = self._tree_range(iteration_range)
+        flat = self._explain_on_device(X, t_begin, t_end, shap=False)
+        if flat is not None:
+            hip = ops.backend_for(X.device)
+            return hip.pred_leaf(flat, X, t_begin, t_end).cpu().numpy()
+        return torch_ref.pred_leaf(self._cpu_flat_forest(), X.cpu(), t_begin, t_end).numpy()
 
     def get_score(self, fmap="", importance_type="weight"):
         """Feature importances (weight / gain / total_gain / cover /
@@ -398,50 +490,90 @@ class Booster:
             dumps.append("\n".join(lines) + "\n")
         return dumps
 
-    def _pred_contribs(self, X, approx=False):
-        """Feature contributions, host.
-
-        Exact TreeSHAP (Lundberg Algorithm 2; parallel C++ over rows) by
-        default — parity with the reference's native pred_contribs path
-        (reference test_abalone.py:65). `approx=True` keeps the fast
-        Saabas approximation (xgboost's approx_contribs=True).
-        Returns (n, f+1) for single-output, (n, k, f+1) for multiclass;
-        rows sum to the margin (additivity).
-        """
-        n = X.shape[0]
-        f = self.num_features or X.shape[1]
+    def _linear_contribs(self, X, base_margin):
+        """gblinear contributions (n, k, f+1) float64: x_j * w_j (missing
+        values contribute 0), bias column = linear bias + starting margin."""
+        n, f = X.shape
         k = self.n_outputs
-        if approx:
-            Xc = X.cpu().numpy()
-            out = np.zeros((n, f + 1), dtype=np.float32)
-            out[:, -1] = self.objective().base_margin(self.base_score)
-            for tree in self.trees:
-                self._saabas(tree, Xc, out)
-            return out
+        phi = torch.zeros((n, k, f + 1), dtype=torch.float64, device=X.device)
+        if self.linear_model is not None:
+            w = self.linear_model.weights.to(X.device).to(torch.float64).reshape(f, k)
+            b = self.linear_model.bias.to(X.device).to(torch.float64).reshape(k)
+            x = torch.nan_to_num(X, nan=0.0).to(torch.float64)
+            phi[:, :, :f] = x.unsqueeze(1) * w.t().unsqueeze(0)
+            phi[:, :, f] = b.unsqueeze(0)
+        phi[:, :, f] += self._bias_rows(n, base_margin, X.device)
+        return phi
+
+    def _pred_contribs(self, X, approx=False, iteration_range=None, base_margin=None):
+        """Feature contributions of the rounds in `iteration_range`.
+
+        Exact TreeSHAP by default — parity with the reference's native
+        pred_contribs path (reference test_abalone.py:65): the path-form
+        HIP kernel when X is on the GPU and the forest is within the device
+        limits, else Lundberg's recursion in parallel C++ on the host.
+        `approx=True` is the Saabas approximation (xgboost's
+        approx_contribs=True), vectorized over the flat forest on X's
+        device. Returns (n, f+1) for single-output, (n, k, f+1) for
+        multiclass; rows sum to the margin (additivity). A DMatrix
+        base_margin replaces base_score in the bias column, per row.
+        """
         from ..ops import torch_ref
 
-        flat = self._cpu_flat_forest()
-        phi = torch_ref.tree_shap(flat, X.cpu(), k)  # (n, k, f+1) float64
-        ev = torch_ref.tree_expected_values(flat, k)
-        base = self.objective().base_margin(self.base_score)
-        phi[:, :, -1] += ev.unsqueeze(0) + float(base)
-        out = phi.to(torch.float32).numpy()
+        n = X.shape[0]
+        k = self.n_outputs
+        if self.booster_type == "gblinear":
+            phi = self._linear_contribs(X, base_margin)
+            out = phi.to(torch.float32).cpu().numpy()
+            return out[:, 0, :] if k == 1 else out
+        t_begin, t_end = self._tree_range(iteration_range)
+        if approx:
+            if X.device.type == "cuda" and ops.backend_for(X.device).NAME == "hip":
+                flat = self._device_flat_forest(X.device, with_paths=False)
+            else:
+                X = X.cpu()
+                flat = self._cpu_flat_forest()
+            phi = torch_ref.saabas_contribs(flat, X, k, t_begin, t_end)
+        else:
+            flat = self._explain_on_device(X, t_begin, t_end, shap=True)
+            if flat is not None:
+                phi = ops.backend_for(X.device).tree_shap(flat, X, k, t_begin, t_end)
+            else:
+                phi = torch_ref.tree_shap(self._cpu_flat_forest(), X.cpu(), k, t_begin, t_end)
+            if t_end > t_begin:
+                phi[:, :, -1] += self._expected_values(t_begin, t_end).to(phi.device).unsqueeze(0)
+        phi[:, :, -1] += self._bias_rows(n, base_margin, phi.device)
+        out = phi.to(torch.float32).cpu().numpy()
         return out[:, 0, :] if k == 1 else out
 
-    @staticmethod
-    def _saabas(tree, X, out):
-        mean_value = tree.value  # base_weights as node expectations
-        for i in range(X.shape[0]):
-            nid = 0
-            while tree.left[nid] >= 0:
-                fv = X[i, tree.feature[nid]]
-                if np.isnan(fv):
-                    nxt = tree.left[nid] if tree.default_left[nid] else tree.right[nid]
-                else:
-                    nxt = tree.left[nid] if fv < tree.threshold[nid] else tree.right[nid]
-                out[i, tree.feature[nid]] += mean_value[nxt] - mean_value[nid]
-                nid = nxt
-            out[i, -1] += mean_value[0]
+    def _pred_interactions(self, X, iteration_range=None, base_margin=None):
+        """SHAP interaction values: (n, f+1, f+1), or (n, k, f+1, f+1) for
+        multiclass, float32. Symmetric; row sums equal pred_contribs; the
+        bias sits in cell [f, f] and the rest of the last row and column is
+        zero. Same routing as _pred_contribs."""
+        from ..ops import torch_ref
+
+        n, f = X.shape
+        k = self.n_outputs
+        if self.booster_type == "gblinear":
+            phi = self._linear_contribs(X, base_margin)
+            out = torch.diag_embed(phi)  # a linear model has no interactions
+        else:
+            t_begin, t_end = self._tree_range(iteration_range)
+            flat = self._explain_on_device(X, t_begin, t_end, shap=True)
+            if flat is not None:
+                out = ops.backend_for(X.device).tree_shap_interactions(
+                    flat, X, k, t_begin, t_end
+                )
+            else:
+                out = torch_ref.tree_shap_interactions(
+                    self._cpu_flat_forest(), X.cpu(), k, t_begin, t_end
+                )
+            if t_end > t_begin:
+                out[:, :, f, f] += self._expected_values(t_begin, t_end).to(out.device).unsqueeze(0)
+            out[:, :, f, f] += self._bias_rows(n, base_margin, out.device)
+        out = out.to(torch.float32).cpu().numpy()
+        return out[:, 0] if k == 1 else out
 
     # -- serialization -----------------------------------------------------
     def _tree_to_json(self, tree, tree_id):

@@ -1244,6 +1244,242 @@ __global__ __launch_bounds__(HIST_BLOCK) void predict_kernel(
   }
 }
 
+// leaf index per (row, tree): the predict_kernel traversal writing the
+// tree-local leaf id (xgboost pred_leaf semantics). One thread per
+// (row, tree), grid-strided.
+__global__ __launch_bounds__(HIST_BLOCK) void pred_leaf_kernel(
+    const float* __restrict__ X, long long n, int nfeat,
+    const int* __restrict__ left, const int* __restrict__ right,
+    const int* __restrict__ feat, const float* __restrict__ thresh,
+    const unsigned char* __restrict__ defl, const int* __restrict__ tree_root,
+    int t_begin, int T, int* __restrict__ out) {
+  const long long total = n * (long long)T;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += step) {
+    const long long row = idx / T;
+    const int t = (int)(idx - row * T);
+    const float* xr = X + row * nfeat;
+    const int root = tree_root[t_begin + t];
+    int nid = root;
+    int l;
+    while ((l = left[nid]) >= 0) {
+      const float fv = xr[feat[nid]];
+      const bool goleft = isnan(fv) ? (defl[nid] != 0) : (fv < thresh[nid]);
+      nid = goleft ? l : right[nid];
+    }
+    out[idx] = nid - root;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// path-form exact TreeSHAP (contributions + interactions)
+// ---------------------------------------------------------------------------
+//
+// The host (ops/shap_paths.py) turns every leaf into one path whose splits
+// are merged per feature, so a path never holds a feature twice and the
+// recursive algorithm's unwind-on-duplicate step disappears. A work item is
+// one (row, tree-chunk); it is owned by a LANE GROUP of width W (power of
+// two >= the longest path incl. the dummy root element), 64/W groups per
+// wave, one lane per path element. Permutation weights are built with the
+// EXTEND recurrence passed between lanes with __shfl/__shfl_up at width W;
+// every lane then computes its own unwound sum. All arithmetic is fp64.
+// No per-thread arrays: every path quantity is one scalar per lane.
+//
+// Every loop bound (paths per chunk, path length, Lmax) comes from the
+// host-built tables; shuffles run unconditionally with a grid-uniform trip
+// count (Lmax) and only the arithmetic is predicated on the path length,
+// so all W lanes of a group always execute the same cross-lane ops.
+
+#define SHAP_BLOCK 256
+#define SHAP_F_NAN 1     // missing values follow this path on this feature
+#define SHAP_F_LO 2      // path has a right turn on this feature (x >= lo)
+#define SHAP_F_HI 4      // path has a left turn on this feature  (x <  hi)
+
+__device__ inline double shap_one_fraction(float x, float lo, float hi, int flags) {
+  if (isnan(x)) return (flags & SHAP_F_NAN) ? 1.0 : 0.0;
+  const bool ok = (!(flags & SHAP_F_LO) || x >= lo) && (!(flags & SHAP_F_HI) || x < hi);
+  return ok ? 1.0 : 0.0;
+}
+
+// Lane `gl` of a W-wide group holds element gl (z, o) of a path of `len`
+// elements (element 0 = dummy root, z = o = 1). Returns the unwound
+// permutation-weight sum for this lane's element. Must be called by all W
+// lanes of the group; `lmax` (>= len, <= W) is the uniform shuffle bound.
+__device__ inline double shap_unwound_sum(double z, double o, int gl, int len, int lmax,
+                                          int W) {
+  double w = gl == 0 ? 1.0 : 0.0;
+  for (int d = 1; d < lmax; ++d) {
+    const double zd = __shfl(z, d, W);
+    const double od = __shfl(o, d, W);
+    const double wl = __shfl_up(w, 1, W);
+    if (d < len) {
+      const double inv = 1.0 / (d + 1);
+      double nw = 0.0;
+      if (gl <= d) {
+        nw = zd * w * (d - gl) * inv;
+        if (gl > 0) nw += od * wl * gl * inv;
+      }
+      w = nw;
+    }
+  }
+  const int D = len - 1;
+  double next = __shfl(w, D > 0 ? D : 0, W);
+  double total = 0.0;
+  for (int j = lmax - 2; j >= 0; --j) {
+    const double wj = __shfl(w, j, W);
+    if (j < D) {
+      if (o != 0.0) {
+        const double tmp = next * (D + 1) / ((j + 1) * o);
+        total += tmp;
+        next = wj - tmp * z * (D - j) / (double)(D + 1);
+      } else if (z != 0.0) {
+        total += (wj / z) * (D + 1) / (double)(D - j);
+      }
+    }
+  }
+  return total;
+}
+
+// out: (n_chunks, n, k, nfeat+1) fp64 partials, bias column untouched.
+// A group exclusively owns out[chunk, row, :, :] — nothing is shared
+// between groups, so there are no atomics; the caller reduces the chunk
+// axis with a fixed-order sum. The running phi slab lives in LDS (one
+// slab of k*(nfeat+1) doubles per group) and is flushed once per item.
+__global__ __launch_bounds__(SHAP_BLOCK) void shap_paths_kernel(
+    const float* __restrict__ X, long long n, int nfeat,
+    const int* __restrict__ elem_feat, const float* __restrict__ elem_lo,
+    const float* __restrict__ elem_hi, const unsigned char* __restrict__ elem_flags,
+    const double* __restrict__ elem_z, const int* __restrict__ path_off,
+    const float* __restrict__ path_value, const int* __restrict__ path_cls,
+    const int* __restrict__ tree_path_ptr, int t_begin, int t_end,
+    double* __restrict__ out, int k, int n_chunks, int trees_per_chunk, int W, int lmax) {
+  extern __shared__ double shap_slab[];
+  const int gpb = SHAP_BLOCK / W;
+  const int g = threadIdx.x / W;
+  const int gl = threadIdx.x - g * W;
+  const int ncols = nfeat + 1;
+  const int slab_n = k * ncols;
+  double* slab = shap_slab + (long long)g * slab_n;
+  for (int i = gl; i < slab_n; i += W) slab[i] = 0.0;
+
+  const long long total = n * (long long)n_chunks;
+  const long long ngroups = (long long)gridDim.x * gpb;
+  for (long long item = (long long)blockIdx.x * gpb + g; item < total; item += ngroups) {
+    // chunk-major items: neighbouring groups share a chunk, so a wave walks
+    // one path list in lock-step and the table loads broadcast
+    const long long c = item / n;
+    const long long row = item - c * n;
+    const int ts = t_begin + (int)c * trees_per_chunk;
+    const int te = min(t_end, ts + trees_per_chunk);
+    const int p0 = tree_path_ptr[ts];
+    const int p1 = tree_path_ptr[te];
+    const float* xr = X + row * nfeat;
+    for (int p = p0; p < p1; ++p) {
+      const int off = path_off[p];
+      const int len = path_off[p + 1] - off + 1;  // + dummy root element
+      const bool mine = gl > 0 && gl < len;
+      double z = 1.0, o = 1.0;
+      int fidx = -1;
+      if (mine) {
+        const int e = off + gl - 1;
+        fidx = elem_feat[e];
+        z = elem_z[e];
+        o = shap_one_fraction(xr[fidx], elem_lo[e], elem_hi[e], elem_flags[e]);
+      }
+      const double s = shap_unwound_sum(z, o, gl, len, lmax, W);
+      // Plain LDS read-modify-write. Within one path no two lanes of a
+      // group hit the same cell (merged paths hold a feature once) and
+      // groups own disjoint slabs. Across paths a cell may be written by
+      // one lane and read by another lane of the SAME wave: a wave's DS
+      // instructions execute in issue order, and the wavefront fence +
+      // wave barrier below keep the compiler from moving them.
+      if (mine) slab[path_cls[p] * ncols + fidx] += s * (o - z) * (double)path_value[p];
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    double* orow = out + item * slab_n;
+    for (int i = gl; i < slab_n; i += W) {
+      orow[i] = slab[i];
+      slab[i] = 0.0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// out: (n_chunks, n, k, nfeat+1, nfeat+1) fp64 partials, off-diagonal
+// cells only. For each path and each element j of it, the remaining
+// elements' contributions are computed with j removed from the path
+// (compacted across lanes); the leaf value scaled by o_j (j "on") minus
+// z_j (j "off"), halved, lands in out[cls, d_i, d_j]. Paths without j
+// cancel and are never touched: O(L^3) per path.
+// The (nfeat+1)^2 slab is too large for LDS, so a group accumulates in its
+// exclusively owned global slice. Within one path every (d_i, d_j) cell is
+// written once; between paths a workgroup-scope fence (vmcnt(0): the
+// group's stores have reached the CU's L1/L2 path that its later loads
+// use) orders one lane's store before another lane's later load.
+__global__ __launch_bounds__(SHAP_BLOCK) void shap_interactions_kernel(
+    const float* __restrict__ X, long long n, int nfeat,
+    const int* __restrict__ elem_feat, const float* __restrict__ elem_lo,
+    const float* __restrict__ elem_hi, const unsigned char* __restrict__ elem_flags,
+    const double* __restrict__ elem_z, const int* __restrict__ path_off,
+    const float* __restrict__ path_value, const int* __restrict__ path_cls,
+    const int* __restrict__ tree_path_ptr, int t_begin, int t_end,
+    double* out, int k, int n_chunks, int trees_per_chunk, int W, int lmax) {
+  const int gpb = SHAP_BLOCK / W;
+  const int g = threadIdx.x / W;
+  const int gl = threadIdx.x - g * W;
+  const int ncols = nfeat + 1;
+  const long long slab_n = (long long)k * ncols * ncols;
+  const int lmax_c = lmax > 1 ? lmax - 1 : 1;  // longest path with one element removed
+
+  const long long total = n * (long long)n_chunks;
+  const long long ngroups = (long long)gridDim.x * gpb;
+  for (long long item = (long long)blockIdx.x * gpb + g; item < total; item += ngroups) {
+    const long long c = item / n;
+    const long long row = item - c * n;
+    const int ts = t_begin + (int)c * trees_per_chunk;
+    const int te = min(t_end, ts + trees_per_chunk);
+    const int p0 = tree_path_ptr[ts];
+    const int p1 = tree_path_ptr[te];
+    const float* xr = X + row * nfeat;
+    double* oslab = out + item * slab_n;
+    for (int p = p0; p < p1; ++p) {
+      const int off = path_off[p];
+      const int len = path_off[p + 1] - off + 1;
+      double z = 1.0, o = 1.0;
+      int fidx = -1;
+      if (gl > 0 && gl < len) {
+        const int e = off + gl - 1;
+        fidx = elem_feat[e];
+        z = elem_z[e];
+        o = shap_one_fraction(xr[fidx], elem_lo[e], elem_hi[e], elem_flags[e]);
+      }
+      const double v = (double)path_value[p];
+      double* cslab = oslab + (long long)path_cls[p] * ncols * ncols;
+      for (int j = 1; j < lmax; ++j) {
+        const double zj = __shfl(z, j, W);
+        const double oj = __shfl(o, j, W);
+        const int fj = __shfl(fidx, j, W);
+        // compact the path around j: lane gl takes element gl (< j) or gl+1
+        const int src = min(gl < j ? gl : gl + 1, W - 1);
+        const double zc = __shfl(z, src, W);
+        const double oc = __shfl(o, src, W);
+        const int fc = __shfl(fidx, src, W);
+        const bool act = j < len;
+        const int len_c = act ? len - 1 : 1;
+        const double s = shap_unwound_sum(zc, oc, gl, len_c, lmax_c, W);
+        if (act && gl > 0 && gl < len_c && oj != zj) {
+          cslab[(long long)fc * ncols + fj] += 0.5 * (oj - zj) * s * (oc - zc) * v;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
@@ -1329,6 +1565,133 @@ void predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                      tree_root.data_ptr<int>(), tree_cls.data_ptr<int>(),
                      (int)t_begin, (int)t_end, out.data_ptr<float>(), (int)k, (int)n_chunks,
                      (int)trees_per_chunk);
+}
+
+#define CHECK_GPU_DENSE(x, dt)                                                          \
+  TORCH_CHECK_VALUE(x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt,          \
+                    #x " must be a contiguous ROCm device tensor of the expected dtype")
+
+void pred_leaf(torch::Tensor X, torch::Tensor left, torch::Tensor right, torch::Tensor feat,
+               torch::Tensor thresh, torch::Tensor defl, torch::Tensor tree_root,
+               int64_t t_begin, int64_t t_end, int64_t max_feature, torch::Tensor out) {
+  CHECK_GPU_DENSE(X, torch::kFloat32);
+  CHECK_GPU_DENSE(left, torch::kInt32);
+  CHECK_GPU_DENSE(right, torch::kInt32);
+  CHECK_GPU_DENSE(feat, torch::kInt32);
+  CHECK_GPU_DENSE(thresh, torch::kFloat32);
+  CHECK_GPU_DENSE(defl, torch::kUInt8);
+  CHECK_GPU_DENSE(tree_root, torch::kInt32);
+  CHECK_GPU_DENSE(out, torch::kInt32);
+  TORCH_CHECK_VALUE(X.dim() == 2, "X must be (n, f)");
+  TORCH_CHECK_VALUE(max_feature < X.size(1), "X has ", X.size(1),
+                    " columns but the forest splits on feature ", max_feature);
+  TORCH_CHECK_VALUE(0 <= t_begin && t_begin <= t_end && t_end <= tree_root.numel(),
+                    "tree range out of bounds");
+  const long long n = X.size(0);
+  const long long T = t_end - t_begin;
+  TORCH_CHECK_VALUE(out.numel() == n * T, "out must be (n, T)");
+  const long long total = n * T;
+  if (total == 0) return;
+  const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 4096);
+  hipLaunchKernelGGL(pred_leaf_kernel, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
+                     X.data_ptr<float>(), n, (int)X.size(1), left.data_ptr<int>(),
+                     right.data_ptr<int>(), feat.data_ptr<int>(), thresh.data_ptr<float>(),
+                     defl.data_ptr<unsigned char>(), tree_root.data_ptr<int>(), (int)t_begin,
+                     (int)T, out.data_ptr<int>());
+}
+
+// shared argument validation for the two path-form TreeSHAP launchers;
+// returns the grid size. `cells` = doubles per (chunk, row) output slice.
+static int shap_check(torch::Tensor X, torch::Tensor elem_feat, torch::Tensor elem_lo,
+                      torch::Tensor elem_hi, torch::Tensor elem_flags, torch::Tensor elem_z,
+                      torch::Tensor path_off, torch::Tensor path_value,
+                      torch::Tensor path_cls, torch::Tensor tree_path_ptr, int64_t t_begin,
+                      int64_t t_end, torch::Tensor out, int64_t k, int64_t n_chunks,
+                      int64_t trees_per_chunk, int64_t W, int64_t lmax, int64_t max_feature,
+                      int64_t cells) {
+  CHECK_GPU_DENSE(X, torch::kFloat32);
+  CHECK_GPU_DENSE(elem_feat, torch::kInt32);
+  CHECK_GPU_DENSE(elem_lo, torch::kFloat32);
+  CHECK_GPU_DENSE(elem_hi, torch::kFloat32);
+  CHECK_GPU_DENSE(elem_flags, torch::kUInt8);
+  CHECK_GPU_DENSE(elem_z, torch::kFloat64);
+  CHECK_GPU_DENSE(path_off, torch::kInt32);
+  CHECK_GPU_DENSE(path_value, torch::kFloat32);
+  CHECK_GPU_DENSE(path_cls, torch::kInt32);
+  CHECK_GPU_DENSE(tree_path_ptr, torch::kInt32);
+  CHECK_GPU_DENSE(out, torch::kFloat64);
+  TORCH_CHECK_VALUE(X.dim() == 2, "X must be (n, f)");
+  TORCH_CHECK_VALUE(max_feature < X.size(1), "X has ", X.size(1),
+                    " columns but the forest splits on feature ", max_feature);
+  TORCH_CHECK_VALUE(lmax >= 1 && lmax <= WAVE, "path length ", lmax, " exceeds the wave width");
+  TORCH_CHECK_VALUE(W >= lmax && W <= WAVE && (W & (W - 1)) == 0,
+                    "lane-group width must be a power of two in [lmax, 64]");
+  TORCH_CHECK_VALUE(0 <= t_begin && t_begin <= t_end && t_end < tree_path_ptr.numel(),
+                    "tree range out of bounds");
+  TORCH_CHECK_VALUE(k >= 1 && n_chunks >= 1 && trees_per_chunk >= 1 &&
+                        n_chunks * trees_per_chunk >= t_end - t_begin &&
+                        (n_chunks - 1) * trees_per_chunk <= t_end - t_begin,
+                    "bad tree chunking");
+  const int64_t n_paths = path_off.numel() - 1;
+  TORCH_CHECK_VALUE(n_paths >= 0 && path_value.numel() == n_paths && path_cls.numel() == n_paths,
+                    "path tables disagree");
+  const int64_t n_elem = elem_feat.numel();
+  TORCH_CHECK_VALUE(elem_lo.numel() == n_elem && elem_hi.numel() == n_elem &&
+                        elem_flags.numel() == n_elem && elem_z.numel() == n_elem,
+                    "element tables disagree");
+  const long long total = (long long)X.size(0) * n_chunks;
+  TORCH_CHECK_VALUE(out.numel() == total * cells, "partial buffer has the wrong size");
+  const long long gpb = SHAP_BLOCK / W;
+  return (int)std::max<long long>(1, std::min<long long>((total + gpb - 1) / gpb, 8192));
+}
+
+void tree_shap_paths(torch::Tensor X, torch::Tensor elem_feat, torch::Tensor elem_lo,
+                     torch::Tensor elem_hi, torch::Tensor elem_flags, torch::Tensor elem_z,
+                     torch::Tensor path_off, torch::Tensor path_value, torch::Tensor path_cls,
+                     torch::Tensor tree_path_ptr, int64_t t_begin, int64_t t_end,
+                     torch::Tensor out, int64_t k, int64_t n_chunks, int64_t trees_per_chunk,
+                     int64_t W, int64_t lmax, int64_t max_feature) {
+  const int64_t ncols = X.dim() == 2 ? X.size(1) + 1 : 1;
+  const int grid = shap_check(X, elem_feat, elem_lo, elem_hi, elem_flags, elem_z, path_off,
+                              path_value, path_cls, tree_path_ptr, t_begin, t_end, out, k,
+                              n_chunks, trees_per_chunk, W, lmax, max_feature, k * ncols);
+  const size_t lds_bytes = (size_t)(SHAP_BLOCK / W) * k * ncols * sizeof(double);
+  TORCH_CHECK_VALUE(lds_bytes <= 64 * 1024, "phi slab does not fit the LDS budget");
+  if (X.size(0) == 0 || t_end == t_begin) return;
+  hipLaunchKernelGGL(shap_paths_kernel, dim3(grid), dim3(SHAP_BLOCK), lds_bytes,
+                     current_stream(), X.data_ptr<float>(), (long long)X.size(0),
+                     (int)X.size(1), elem_feat.data_ptr<int>(), elem_lo.data_ptr<float>(),
+                     elem_hi.data_ptr<float>(), elem_flags.data_ptr<unsigned char>(),
+                     elem_z.data_ptr<double>(), path_off.data_ptr<int>(),
+                     path_value.data_ptr<float>(), path_cls.data_ptr<int>(),
+                     tree_path_ptr.data_ptr<int>(), (int)t_begin, (int)t_end,
+                     out.data_ptr<double>(), (int)k, (int)n_chunks, (int)trees_per_chunk,
+                     (int)W, (int)lmax);
+}
+
+void tree_shap_interactions_paths(torch::Tensor X, torch::Tensor elem_feat,
+                                  torch::Tensor elem_lo, torch::Tensor elem_hi,
+                                  torch::Tensor elem_flags, torch::Tensor elem_z,
+                                  torch::Tensor path_off, torch::Tensor path_value,
+                                  torch::Tensor path_cls, torch::Tensor tree_path_ptr,
+                                  int64_t t_begin, int64_t t_end, torch::Tensor out, int64_t k,
+                                  int64_t n_chunks, int64_t trees_per_chunk, int64_t W,
+                                  int64_t lmax, int64_t max_feature) {
+  const int64_t ncols = X.dim() == 2 ? X.size(1) + 1 : 1;
+  const int grid = shap_check(X, elem_feat, elem_lo, elem_hi, elem_flags, elem_z, path_off,
+                              path_value, path_cls, tree_path_ptr, t_begin, t_end, out, k,
+                              n_chunks, trees_per_chunk, W, lmax, max_feature,
+                              k * ncols * ncols);
+  if (X.size(0) == 0 || t_end == t_begin) return;
+  hipLaunchKernelGGL(shap_interactions_kernel, dim3(grid), dim3(SHAP_BLOCK), 0,
+                     current_stream(), X.data_ptr<float>(), (long long)X.size(0),
+                     (int)X.size(1), elem_feat.data_ptr<int>(), elem_lo.data_ptr<float>(),
+                     elem_hi.data_ptr<float>(), elem_flags.data_ptr<unsigned char>(),
+                     elem_z.data_ptr<double>(), path_off.data_ptr<int>(),
+                     path_value.data_ptr<float>(), path_cls.data_ptr<int>(),
+                     tree_path_ptr.data_ptr<int>(), (int)t_begin, (int)t_end,
+                     out.data_ptr<double>(), (int)k, (int)n_chunks, (int)trees_per_chunk,
+                     (int)W, (int)lmax);
 }
 
 void hist_build_compact(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor jobs,
@@ -1748,5 +2111,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("leaf_update", &leaf_update, "batched leaf value scatter into margins");
   m.def("predict_forest", &predict_forest, "batched dense forest traversal");
   m.def("grad_fused", &grad_fused, "one-pass gradient + absmax partials");
+  m.def("pred_leaf", &pred_leaf, "leaf index per (row, tree)");
+  m.def("tree_shap_paths", &tree_shap_paths, "path-form exact TreeSHAP contributions");
+  m.def("tree_shap_interactions_paths", &tree_shap_interactions_paths,
+        "path-form exact TreeSHAP interaction values (off-diagonal)");
   m.attr("_built_for") = "gfx950";
 }

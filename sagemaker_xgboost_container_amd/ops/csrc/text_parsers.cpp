@@ -380,22 +380,44 @@ struct TreeView {
   const float* cover;
 };
 
-// recursion: `path` region for this call starts after the parent's copy
+// recursion: `path` region for this call starts after the parent's copy.
+// `condition` selects Lundberg's conditional form used for interaction
+// values: 0 = plain TreeSHAP, +1 = `condition_feature` fixed "on" (always
+// follows x), -1 = fixed "off" (always averaged out). The conditioned
+// feature never enters the path; its effect is carried by
+// `condition_fraction`, which scales the leaf value. With condition == 0
+// the fraction stays exactly 1.0 and the arithmetic is unchanged.
 void recurse(const TreeView& t, const float* xr, double* phi, int node,
              int unique_depth, PathElement* parent_path, double parent_zero_fraction,
-             double parent_one_fraction, int parent_feature_index) {
+             double parent_one_fraction, int parent_feature_index, int condition = 0,
+             int condition_feature = -1, double condition_fraction = 1.0) {
+  if (condition_fraction == 0.0) return;
   PathElement* path = parent_path + unique_depth + 1;
   for (int i = 0; i < unique_depth; ++i) path[i] = parent_path[i];
-  extend_path(path, unique_depth, parent_zero_fraction, parent_one_fraction,
-              parent_feature_index);
+  if (condition == 0 || condition_feature != parent_feature_index) {
+    extend_path(path, unique_depth, parent_zero_fraction, parent_one_fraction,
+                parent_feature_index);
+  } else {
+    // the parent split on the conditioned feature and passed its whole
+    // path (unique_depth + 1 elements) through unextended
+    path[unique_depth] = parent_path[unique_depth];
+  }
 
   const int l = t.left[node];
   if (l < 0) {  // leaf
     const double v = t.value[node];
-    for (int i = 1; i <= unique_depth; ++i) {
-      const double w = unwound_path_sum(path, unique_depth, i);
-      phi[path[i].feature_index] +=
-          w * (path[i].one_fraction - path[i].zero_fraction) * v;
+    if (condition == 0) {
+      for (int i = 1; i <= unique_depth; ++i) {
+        const double w = unwound_path_sum(path, unique_depth, i);
+        phi[path[i].feature_index] +=
+            w * (path[i].one_fraction - path[i].zero_fraction) * v;
+      }
+    } else {
+      for (int i = 1; i <= unique_depth; ++i) {
+        const double w = unwound_path_sum(path, unique_depth, i);
+        phi[path[i].feature_index] +=
+            w * (path[i].one_fraction - path[i].zero_fraction) * v * condition_fraction;
+      }
     }
     return;
   }
@@ -423,10 +445,25 @@ void recurse(const TreeView& t, const float* xr, double* phi, int node,
     unique_depth -= 1;
   }
 
+  // a split on the conditioned feature does not lengthen the path: "on"
+  // sends everything down the hot child, "off" splits by cover
+  double hot_condition_fraction = condition_fraction;
+  double cold_condition_fraction = condition_fraction;
+  if (condition > 0 && split == condition_feature) {
+    cold_condition_fraction = 0.0;
+    unique_depth -= 1;
+  } else if (condition < 0 && split == condition_feature) {
+    hot_condition_fraction *= hot_zero_fraction;
+    cold_condition_fraction *= cold_zero_fraction;
+    unique_depth -= 1;
+  }
+
   recurse(t, xr, phi, hot, unique_depth + 1, path,
-          hot_zero_fraction * incoming_zero_fraction, incoming_one_fraction, split);
+          hot_zero_fraction * incoming_zero_fraction, incoming_one_fraction, split,
+          condition, condition_feature, hot_condition_fraction);
   recurse(t, xr, phi, cold, unique_depth + 1, path,
-          cold_zero_fraction * incoming_zero_fraction, 0.0, split);
+          cold_zero_fraction * incoming_zero_fraction, 0.0, split,
+          condition, condition_feature, cold_condition_fraction);
 }
 
 }  // namespace treeshap
@@ -436,7 +473,8 @@ void tree_shap_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                    torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                    torch::Tensor value, torch::Tensor cover, torch::Tensor tree_root,
                    torch::Tensor tree_cls, int64_t t_begin, int64_t t_end,
-                   torch::Tensor out_phi, int64_t k, int64_t max_depth) {
+                   torch::Tensor out_phi, int64_t k, int64_t max_depth,
+                   int64_t condition, int64_t condition_feature) {
   const float* x = X.data_ptr<float>();
   const int64_t n = X.size(0);
   const int64_t nf = X.size(1);
@@ -458,7 +496,8 @@ void tree_shap_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
       const float* xr = x + row * nf;
       for (int64_t t = t_begin; t < t_end; ++t) {
         double* phi = op + (row * k + cls[t]) * ncols;
-        treeshap::recurse(tv, xr, phi, roots[t], 0, path.data(), 1.0, 1.0, -1);
+        treeshap::recurse(tv, xr, phi, roots[t], 0, path.data(), 1.0, 1.0, -1,
+                          (int)condition, (int)condition_feature, 1.0);
       }
     }
   });
@@ -506,6 +545,12 @@ void init_text_parsers(pybind11::module_& m) {
   m.def("predict_forest_cpu", &predict_forest_cpu, "parallel host forest traversal");
   m.def("parse_csv", &parse_csv, "multi-threaded csv -> dense float32 parser",
         pybind11::arg("text"), pybind11::arg("delimiter") = ",", pybind11::arg("nthreads") = 0);
-  m.def("tree_shap_cpu", &tree_shap_cpu, "exact TreeSHAP contributions (parallel rows)");
+  namespace py = pybind11;
+  m.def("tree_shap_cpu", &tree_shap_cpu, "exact TreeSHAP contributions (parallel rows)",
+        py::arg("X"), py::arg("left"), py::arg("right"), py::arg("feat"), py::arg("thresh"),
+        py::arg("defl"), py::arg("value"), py::arg("cover"), py::arg("tree_root"),
+        py::arg("tree_cls"), py::arg("t_begin"), py::arg("t_end"), py::arg("out_phi"),
+        py::arg("k"), py::arg("max_depth"), py::arg("condition") = 0,
+        py::arg("condition_feature") = -1);
   m.def("pred_leaf_cpu", &pred_leaf_cpu, "parallel leaf-index traversal");
 }

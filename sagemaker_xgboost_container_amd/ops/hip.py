@@ -371,6 +371,15 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
         "value": torch.from_numpy(value).to(device),
         "tree_root": torch.from_numpy(offsets[:-1]).to(device),
         "tree_cls": torch.from_numpy(np.asarray(tree_info, dtype=np.int32)).to(device),
+        "cover": torch.from_numpy(
+            np.concatenate([np.asarray(t.sum_hess, dtype=np.float32) for t in trees])
+        ).to(device),
+        # largest split feature per tree (-1 for a stump): lets the leaf
+        # launcher reject a too-narrow X without a device round trip
+        "tree_max_feature": np.asarray(
+            [int(t.feature[t.left >= 0].max()) if (t.left >= 0).any() else -1 for t in trees],
+            dtype=np.int64,
+        ),
         "n_trees": len(trees),
     }
 
@@ -381,6 +390,171 @@ def predict_forest_flat(flat, X, k, t_begin=0, t_end=None):
     if t_end <= t_begin:
         return torch.zeros((X.shape[0], k), dtype=torch.float32, device=X.device)
     return _run_predict(X, flat, k, t_begin, t_end)
+
+
+# ---------------------------------------------------------------------------
+# Device explanations: path-form exact TreeSHAP (contributions and
+# interaction values) and leaf indices. Same signatures as the torch_ref
+# host functions; the flat forest must carry the path tables under
+# flat["shap_paths"] (make_shap_paths below).
+# ---------------------------------------------------------------------------
+
+# device limits (the booster routes to the host path beyond them)
+SHAP_MAX_PATH_LEN = 64            # one lane per path element, one wave at most
+SHAP_LDS_BUDGET = 48 * 1024       # phi slabs of all lane groups of a block
+SHAP_PARTIAL_CAP = 256 << 20      # bytes of per-chunk fp64 partials per launch
+_SHAP_BLOCK = 256                 # SHAP_BLOCK in the kernel source
+_SHAP_TARGET_GROUPS = 32768       # (row, tree-chunk) items wanted per launch
+
+
+def make_shap_paths(trees, tree_info, weight_drop, device):
+    """Path tables (ops/shap_paths.py) uploaded to `device`; the per-tree
+    limits stay on the host."""
+    from . import shap_paths as _sp
+
+    host = _sp.make_shap_paths(trees, tree_info, weight_drop)
+    dev = {
+        name: torch.from_numpy(host[name]).to(device)
+        for name in (
+            "elem_feature", "elem_lo", "elem_hi", "elem_flags", "elem_zero_fraction",
+            "path_offset", "path_value", "path_cls", "tree_path_ptr",
+        )
+    }
+    dev["tree_max_len"] = host["tree_max_len"]
+    dev["tree_max_feature"] = host["tree_max_feature"]
+    dev["n_trees"] = len(trees)
+    return dev
+
+
+def shap_group_width(L):
+    """Lane-group width: smallest power of two >= the longest path."""
+    W = 1
+    while W < L:
+        W *= 2
+    return W
+
+
+def shap_limits(paths, k, nfeat, t_begin, t_end):
+    """(L, max_feature, fits): path-length / feature limits of the tree
+    range and whether the contribution kernel's LDS slabs fit."""
+    from . import shap_paths as _sp
+
+    L, max_f = _sp.range_limits(paths, t_begin, t_end)
+    fits = L <= SHAP_MAX_PATH_LEN
+    if fits:
+        groups = _SHAP_BLOCK // shap_group_width(L)
+        fits = groups * k * (nfeat + 1) * 8 <= SHAP_LDS_BUDGET
+    return L, max_f, fits
+
+
+def _shap_prepare(flat, X, k, t_begin, t_end):
+    paths = flat.get("shap_paths")
+    if paths is None:
+        raise ValueError("flat forest carries no path tables (flat['shap_paths'])")
+    if t_end is None:
+        t_end = paths["n_trees"]
+    if not (0 <= t_begin <= t_end <= paths["n_trees"]):
+        raise ValueError(f"tree range [{t_begin}, {t_end}) out of bounds")
+    if not X.is_cuda or X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError("X must be a 2-d float32 ROCm device tensor")
+    X = X.contiguous()
+    L, max_f, _ = shap_limits(paths, k, X.shape[1], t_begin, t_end)
+    if max_f >= X.shape[1]:
+        raise ValueError(
+            f"X has {X.shape[1]} columns but the forest splits on feature {max_f}"
+        )
+    if L > SHAP_MAX_PATH_LEN:
+        raise ValueError(f"path length {L} exceeds the device limit {SHAP_MAX_PATH_LEN}")
+    return paths, X, t_end, L, max_f
+
+
+def _shap_tiles(n, T, cell_bytes):
+    """Yield (row_start, row_end, n_chunks, trees_per_chunk) so that each
+    launch's partial buffer (n_chunks * rows * cell_bytes) stays under
+    SHAP_PARTIAL_CAP and small batches still split the tree axis."""
+    rows_per_tile = max(1, min(n, SHAP_PARTIAL_CAP // max(cell_bytes, 1)))
+    for r0 in range(0, n, rows_per_tile):
+        r1 = min(n, r0 + rows_per_tile)
+        rows = r1 - r0
+        want = max(1, (_SHAP_TARGET_GROUPS + rows - 1) // rows)
+        cap = max(1, SHAP_PARTIAL_CAP // (rows * cell_bytes))
+        n_chunks = int(min(T, want, cap))
+        tpc = (T + n_chunks - 1) // n_chunks
+        n_chunks = (T + tpc - 1) // tpc
+        yield r0, r1, n_chunks, tpc
+
+
+def _launch_shap(kernel, paths, X, k, t_begin, t_end, L, max_f, cells):
+    n = X.shape[0]
+    out = torch.empty((n, cells), dtype=torch.float64, device=X.device)
+    W = shap_group_width(L)
+    for r0, r1, n_chunks, tpc in _shap_tiles(n, t_end - t_begin, cells * 8):
+        Xt = X[r0:r1]
+        part = torch.zeros((n_chunks, r1 - r0, cells), dtype=torch.float64, device=X.device)
+        kernel(
+            Xt, paths["elem_feature"], paths["elem_lo"], paths["elem_hi"],
+            paths["elem_flags"], paths["elem_zero_fraction"], paths["path_offset"],
+            paths["path_value"], paths["path_cls"], paths["tree_path_ptr"],
+            t_begin, t_end, part, k, n_chunks, tpc, W, L, max_f,
+        )
+        out[r0:r1] = part.sum(0)  # fixed-order reduce: deterministic
+    return out
+
+
+def tree_shap(flat, X, k, t_begin=0, t_end=None):
+    """Exact TreeSHAP contributions on the device: (n, k, f+1) float64, bias
+    column NOT filled (same contract as torch_ref.tree_shap)."""
+    paths, X, t_end, L, max_f = _shap_prepare(flat, X, k, t_begin, t_end)
+    n, f = X.shape
+    if n == 0 or t_end <= t_begin:
+        return torch.zeros((n, k, f + 1), dtype=torch.float64, device=X.device)
+    if (_SHAP_BLOCK // shap_group_width(L)) * k * (f + 1) * 8 > SHAP_LDS_BUDGET:
+        raise ValueError("phi slab does not fit the LDS budget")
+    out = _launch_shap(_K.tree_shap_paths, paths, X, k, t_begin, t_end, L, max_f, k * (f + 1))
+    return out.reshape(n, k, f + 1)
+
+
+def tree_shap_interactions(flat, X, k, t_begin=0, t_end=None):
+    """Exact TreeSHAP interaction values on the device: (n, k, f+1, f+1)
+    float64. Off-diagonals come from shap_interactions_kernel; the diagonal
+    is phi_i - sum_{j != i} phi_int[i, j] from a contributions pass. The
+    bias row/column stay zero (the booster fills cell [f, f])."""
+    paths, X, t_end, L, max_f = _shap_prepare(flat, X, k, t_begin, t_end)
+    n, f = X.shape
+    c = f + 1
+    if n == 0 or t_end <= t_begin:
+        return torch.zeros((n, k, c, c), dtype=torch.float64, device=X.device)
+    phi = tree_shap(flat, X, k, t_begin, t_end)
+    out = _launch_shap(
+        _K.tree_shap_interactions_paths, paths, X, k, t_begin, t_end, L, max_f, k * c * c
+    ).reshape(n, k, c, c)
+    diag = phi - out.sum(dim=3)
+    out.diagonal(dim1=2, dim2=3).copy_(diag)
+    return out
+
+
+def pred_leaf(flat, X, t_begin=0, t_end=None):
+    """(n, T) int32 tree-local leaf indices on the device."""
+    if t_end is None:
+        t_end = flat["n_trees"]
+    if not (0 <= t_begin <= t_end <= flat["n_trees"]):
+        raise ValueError(f"tree range [{t_begin}, {t_end}) out of bounds")
+    if not X.is_cuda or X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError("X must be a 2-d float32 ROCm device tensor")
+    X = X.contiguous()
+    T = t_end - t_begin
+    max_f = int(flat["tree_max_feature"][t_begin:t_end].max()) if T > 0 else -1
+    if max_f >= X.shape[1]:
+        raise ValueError(
+            f"X has {X.shape[1]} columns but the forest splits on feature {max_f}"
+        )
+    out = torch.zeros((X.shape[0], T), dtype=torch.int32, device=X.device)
+    if T > 0 and X.shape[0] > 0:
+        _K.pred_leaf(
+            X, flat["left"], flat["right"], flat["feature"], flat["threshold"],
+            flat["default_left"], flat["tree_root"], t_begin, t_end, max_f, out,
+        )
+    return out
 
 
 class TreeState:

@@ -464,9 +464,89 @@ def _py_tree_shap_one(flat, xr, phi, root):
     rec(root, [], 1.0, 1.0, -1)
 
 
-def tree_shap(flat, X, k, t_begin=0, t_end=None):
+def _py_tree_shap_cond_one(flat, xr, phi, root, condition, condition_feature):
+    """Pure-Python conditional TreeSHAP for one (row, tree): Lundberg's
+    form with `condition_feature` fixed on (condition=+1) or off (-1). The
+    conditioned feature never enters the path; it scales the leaf value
+    through the condition fraction. Fallback/oracle for interactions."""
+    import math
+
+    left = flat["left"].numpy()
+    right = flat["right"].numpy()
+    feat = flat["feature"].numpy()
+    thresh = flat["threshold"].numpy()
+    defl = flat["default_left"].numpy()
+    value = flat["value"].numpy()
+    cover = flat["cover"].numpy()
+
+    def leaf_weights(elems):
+        """Unwound sums of a finished path: elems = [(feature, z, o)],
+        duplicate-free. Returns one permutation-weight sum per element."""
+        path = [[-1, 1.0, 1.0, 1.0]]
+        for fi, zf, of in elems:
+            path.append([fi, zf, of, 0.0])
+            d = len(path) - 1
+            for i in range(d - 1, -1, -1):
+                path[i + 1][3] += of * path[i][3] * (i + 1) / (d + 1)
+                path[i][3] = zf * path[i][3] * (d - i) / (d + 1)
+        d = len(path) - 1
+        sums = []
+        for i in range(1, d + 1):
+            of, zf = path[i][2], path[i][1]
+            nxt = path[d][3]
+            total = 0.0
+            for j in range(d - 1, -1, -1):
+                if of != 0:
+                    tmp = nxt * (d + 1) / ((j + 1) * of)
+                    total += tmp
+                    nxt = path[j][3] - tmp * zf * (d - j) / (d + 1)
+                elif zf != 0:
+                    total += (path[j][3] / zf) * (d + 1) / (d - j)
+            sums.append(total)
+        return sums
+
+    def rec(node, elems, cond_fraction):
+        if cond_fraction == 0.0:
+            return
+        l = left[node]
+        if l < 0:
+            for (fi, zf, of), w in zip(elems, leaf_weights(elems)):
+                phi[fi] += w * (of - zf) * value[node] * cond_fraction
+            return
+        r = right[node]
+        split = int(feat[node])
+        fv = xr[split]
+        hot = (l if defl[node] else r) if math.isnan(float(fv)) else (l if fv < thresh[node] else r)
+        cold = r if hot == l else l
+        c = float(cover[node]) if cover[node] > 0 else 1.0
+        hz, cz = float(cover[hot]) / c, float(cover[cold]) / c
+        if split == condition_feature:
+            if condition > 0:
+                rec(hot, elems, cond_fraction)
+            else:
+                rec(hot, elems, cond_fraction * hz)
+                rec(cold, elems, cond_fraction * cz)
+            return
+        izf, iof = 1.0, 1.0
+        rest = elems
+        for idx, (fi, zf, of) in enumerate(elems):
+            if fi == split:  # merge with the earlier split on this feature
+                izf, iof = zf, of
+                rest = elems[:idx] + elems[idx + 1:]
+                break
+        rec(hot, rest + [(split, hz * izf, iof)], cond_fraction)
+        rec(cold, rest + [(split, cz * izf, 0.0)], cond_fraction)
+
+    rec(root, [], 1.0)
+
+
+def tree_shap(flat, X, k, t_begin=0, t_end=None, condition=0, condition_feature=-1):
     """Exact TreeSHAP contributions: (n, k, f+1) float64 (bias column NOT
-    filled — the booster adds expected values + base margin)."""
+    filled — the booster adds expected values + base margin).
+
+    `condition` = +1 / -1 computes Lundberg's conditional contributions
+    with `condition_feature` fixed on / off (the building block of the
+    interaction values); the default 0 is plain TreeSHAP."""
     if t_end is None:
         t_end = flat["n_trees"]
     X = X.cpu().contiguous()
@@ -478,13 +558,17 @@ def tree_shap(flat, X, k, t_begin=0, t_end=None):
         from . import _smxgb_hip as K
 
         i32 = _flat_i32(flat)
-        K.tree_shap_cpu(
+        args = (
             X, i32["left"], i32["right"], i32["feature"],
             flat["threshold"].contiguous(), i32["default_left"],
             flat["value"].contiguous(), flat["cover"].contiguous(),
             i32["tree_root"], i32["tree_cls"], t_begin, t_end, phi, k,
             int(flat.get("max_depth", 32)),
         )
+        if condition:
+            K.tree_shap_cpu(*args, int(condition), int(condition_feature))
+        else:
+            K.tree_shap_cpu(*args)
         return phi
     except ImportError:
         pass
@@ -494,7 +578,92 @@ def tree_shap(flat, X, k, t_begin=0, t_end=None):
     phi_np = phi.numpy()
     for row in range(n):
         for t in range(t_begin, t_end):
-            _py_tree_shap_one(flat, Xn[row], phi_np[row, cls[t]], int(roots[t]))
+            if condition:
+                _py_tree_shap_cond_one(
+                    flat, Xn[row], phi_np[row, cls[t]], int(roots[t]),
+                    condition, condition_feature,
+                )
+            else:
+                _py_tree_shap_one(flat, Xn[row], phi_np[row, cls[t]], int(roots[t]))
+    return phi
+
+
+def split_features(flat, t_begin=0, t_end=None):
+    """Sorted feature indices that trees [t_begin, t_end) split on."""
+    if t_end is None:
+        t_end = flat["n_trees"]
+    if t_end <= t_begin:
+        return []
+    roots = flat["tree_root"]
+    s = int(roots[t_begin])
+    e = int(roots[t_end]) if t_end < flat["n_trees"] else flat["left"].shape[0]
+    internal = flat["left"][s:e] >= 0
+    return sorted(int(v) for v in torch.unique(flat["feature"][s:e][internal]))
+
+
+def tree_shap_interactions(flat, X, k, t_begin=0, t_end=None):
+    """Exact TreeSHAP interaction values: (n, k, f+1, f+1) float64.
+
+    For every feature j the forest splits on, off-diagonal column j is half
+    the difference of the contributions conditioned on j being on and off;
+    features the forest never splits on interact with nothing. The diagonal
+    is phi_i - sum_{j != i} phi_int[i, j]; the bias row/column stay zero
+    (the booster fills cell [f, f])."""
+    if t_end is None:
+        t_end = flat["n_trees"]
+    n, f = X.shape
+    out = torch.zeros((n, k, f + 1, f + 1), dtype=torch.float64)
+    if t_end <= t_begin or n == 0:
+        return out
+    phi = tree_shap(flat, X, k, t_begin, t_end)
+    for j in split_features(flat, t_begin, t_end):
+        on = tree_shap(flat, X, k, t_begin, t_end, condition=1, condition_feature=j)
+        off = tree_shap(flat, X, k, t_begin, t_end, condition=-1, condition_feature=j)
+        out[:, :, :, j] = (on - off) / 2
+        out[:, :, j, j] = 0.0
+    diag = phi - out.sum(dim=3)
+    out.diagonal(dim1=2, dim2=3).copy_(diag)
+    return out
+
+
+def saabas_contribs(flat, X, k, t_begin=0, t_end=None):
+    """Saabas path attribution (xgboost approx_contribs=True) over the flat
+    forest, vectorized on whatever device X and the flat forest live on:
+    (n, k, f+1) float64. Walking each (row, tree) root -> leaf, the change
+    of the node expectation value[next] - value[cur] is credited to the
+    split feature; the bias column collects the root values."""
+    if t_end is None:
+        t_end = flat["n_trees"]
+    n, f = X.shape
+    T = t_end - t_begin
+    phi = torch.zeros((n, k, f + 1), dtype=torch.float64, device=X.device)
+    if T <= 0 or n == 0:
+        return phi
+    left = flat["left"].long()
+    right = flat["right"].long()
+    feat = flat["feature"].long()
+    thresh = flat["threshold"]
+    defl = flat["default_left"].to(torch.bool)
+    value = flat["value"].to(torch.float64)
+    roots = flat["tree_root"][t_begin:t_end].long()
+    cls = flat["tree_cls"][t_begin:t_end].long()
+    phi[:, :, f].index_add_(1, cls, value[roots].unsqueeze(0).expand(n, T).contiguous())
+    node = roots.unsqueeze(0).expand(n, T).contiguous()
+    cls_nt = cls.unsqueeze(0).expand(n, T)
+    flat_phi = phi.view(-1)
+    active = left[node] >= 0
+    while bool(active.any()):
+        cur = node[active]
+        rows = active.nonzero(as_tuple=True)[0]
+        fidx = feat[cur]
+        fv = X[rows, fidx]
+        go_left = torch.where(torch.isnan(fv), defl[cur], fv < thresh[cur])
+        nxt = torch.where(go_left, left[cur], right[cur])
+        flat_phi.index_add_(
+            0, (rows * k + cls_nt[active]) * (f + 1) + fidx, value[nxt] - value[cur]
+        )
+        node[active] = nxt
+        active = left[node] >= 0
     return phi
 
 
