@@ -25,11 +25,16 @@ Backend ops come from ops.backend_for(device): CDNA4 HIP kernels on MI355X,
 torch reference on CPU.
 """
 import heapq
+import logging
+import os
 
+import numpy as np
 import torch
 
 from .. import ops
 from .tree import Tree
+
+logger = logging.getLogger(__name__)
 
 
 class GrowParams:
@@ -76,9 +81,10 @@ class GrowParams:
 
 
 class _Node:
-    __slots__ = ("nid", "parity", "start", "end", "g", "h", "depth", "lower", "upper", "allowed")
+    __slots__ = ("nid", "parity", "start", "end", "g", "h", "depth", "lower", "upper", "allowed", "sum32")
 
-    def __init__(self, nid, parity, start, end, g, h, depth, lower=-float("inf"), upper=float("inf"), allowed=None):
+    def __init__(self, nid, parity, start, end, g, h, depth, lower=-float("inf"), upper=float("inf"), allowed=None,
+                 sum32=None):
         self.nid = nid
         self.parity = parity
         self.start = start
@@ -89,6 +95,10 @@ class _Node:
         self.lower = lower   # monotone-constraint weight bounds
         self.upper = upper
         self.allowed = allowed  # interaction-constraint feature mask (f,) bool or None
+        # (G, H) in the device grower's float32 arithmetic (a right child's
+        # by float32 subtraction from its parent's, as make_level derives
+        # them); None where the per-level loop does not mirror that grower
+        self.sum32 = sum32
 
     @property
     def seg(self):
@@ -106,10 +116,23 @@ class HistGrower:
         self.state = None
         f = qm.num_col
         self.monotone = None
+        self._monotone_host = None  # the same vector as host ints
         if self.p.monotone_constraints:
             mono = list(self.p.monotone_constraints)[:f] + [0] * max(0, f - len(self.p.monotone_constraints))
             if any(mono):
                 self.monotone = torch.tensor(mono, dtype=torch.int8, device=self.device)
+                self._monotone_host = [int(c) for c in mono]
+        # "device" or "per_level": which grower path the last tree took
+        self.grow_path = None
+        # On a backend with a device grower the per-level depthwise loop
+        # reproduces that grower's arithmetic, so both paths grow the same
+        # trees: the root (G, H) rounded to float32 before leaf weights
+        # subtract from it (the device reads node_gh[0] back), and float32
+        # node sums into the split scan. Elsewhere it keeps float64 sums.
+        self._mirror_device = (
+            hasattr(self.backend, "DeviceGrower") and self.p.grow_policy != "lossguide"
+        )
+        self._fallback_logged = False
         self.inter_sets = None
         if self.p.interaction_constraints:
             self.inter_sets = [set(group) for group in self.p.interaction_constraints]
@@ -149,11 +172,29 @@ class HistGrower:
             return node.allowed
         return base_mask & node.allowed
 
-    def _sample_features(self, frac, prev_mask):
+    @staticmethod
+    def _sample_count(frac, avail_count):
+        """How many of `avail_count` features a colsample draw keeps."""
+        if frac >= 1.0:
+            return avail_count
+        return max(1, int(round(frac * avail_count)))
+
+    def _sample_features(self, frac, prev_mask, prev_count=None):
+        """Draw a feature mask of `frac` of the features set in `prev_mask`
+        (all features when None). `prev_count`, the number of features set
+        in `prev_mask` when the caller knows it, selects them without the
+        host sync of nonzero(); the draw is the same either way."""
         f = self.qm.num_col
         if frac >= 1.0:
             return prev_mask
-        avail = torch.arange(f, device=self.device) if prev_mask is None else prev_mask.nonzero().flatten()
+        if prev_mask is None:
+            avail = torch.arange(f, device=self.device)
+        elif prev_count is None:
+            avail = prev_mask.nonzero().flatten()
+        else:
+            # stable sort of the inverted mask lists the set positions
+            # first, in ascending order: nonzero() with a known length
+            avail = torch.sort((~prev_mask).to(torch.uint8), stable=True).indices[:prev_count]
         k = max(1, int(round(frac * avail.numel())))
         perm = torch.randperm(avail.numel(), device=self.device, generator=self.generator)[:k]
         mask = torch.zeros(f, dtype=torch.bool, device=self.device)
@@ -204,23 +245,13 @@ class HistGrower:
 
         # device-autonomous fast path: the whole depthwise tree enqueued
         # with zero host syncs (one readback at the end)
-        import os as _os
-
-        if (
-            hasattr(self.backend, "DeviceGrower")
-            and _os.environ.get("SMXGB_NO_DEVICE_GROW") != "1"
-            and p.grow_policy == "depthwise"
-            and p.max_leaves == 0
-            and 1 <= p.max_depth <= 10
-            and self.monotone is None
-            and self.inter_sets is None
-            and p.colsample_bylevel >= 1.0
-            and p.colsample_bynode >= 1.0
-        ):
+        if self._device_grow_ok():
+            self.grow_path = "device"
             tree, leaf_jobs = self._grow_depthwise_device(gh, scale, cap, tree_mask)
             tree.finalize()
             return tree, leaf_jobs
 
+        self.grow_path = "per_level"
         tree = Tree()
         cached = getattr(gh, "_smxgb_rootsum", None) if rows is None else None
         root_sum = (
@@ -234,8 +265,12 @@ class HistGrower:
         )
         root_sum = self._allreduce(root_sum)
         G, H = float(root_sum[0]), float(root_sum[1])
+        sum32 = None
+        if self._mirror_device:
+            sum32 = (np.float32(G), np.float32(H))
+            G, H = float(sum32[0]), float(sum32[1])
         root = tree.add_node(parent=-1, value=self._weight(G, H) * p.eta, sum_hess=H)
-        root_node = _Node(root, 0, 0, cap, G, H, 0)
+        root_node = _Node(root, 0, 0, cap, G, H, 0, sum32=sum32)
 
         if p.grow_policy == "lossguide":
             leaf_jobs = self._grow_lossguide(tree, gh, scale, root_node, tree_mask)
@@ -243,6 +278,42 @@ class HistGrower:
             leaf_jobs = self._grow_depthwise(tree, gh, scale, root_node, tree_mask)
         tree.finalize()
         return tree, leaf_jobs
+
+    def _constrained(self):
+        """Any hyperparameter that needs per-level or per-node candidate
+        state (monotone / interaction constraints, level or node colsample)."""
+        p = self.p
+        return (
+            self.monotone is not None
+            or self.inter_sets is not None
+            or p.colsample_bylevel < 1.0
+            or p.colsample_bynode < 1.0
+        )
+
+    def _device_fallback_reason(self):
+        """Why this configuration cannot use the device grower (None when
+        it can)."""
+        p = self.p
+        if p.grow_policy != "depthwise":
+            return "grow_policy=%s (lossguide)" % p.grow_policy
+        if p.max_leaves != 0:
+            return "max_leaves=%d" % p.max_leaves
+        if p.max_depth > 10:
+            return "max_depth=%d above 10" % p.max_depth
+        if p.max_depth < 1:
+            return "max_depth=%d" % p.max_depth
+        if self.comm is not None and self._constrained():
+            return "monotone/interaction constraints or level/node colsample with a communicator"
+        return None
+
+    def _device_grow_ok(self):
+        if not hasattr(self.backend, "DeviceGrower") or os.environ.get("SMXGB_NO_DEVICE_GROW") == "1":
+            return False
+        reason = self._device_fallback_reason()
+        if reason is not None and not self._fallback_logged:
+            self._fallback_logged = True
+            logger.debug("device grower not used, growing per level: %s", reason)
+        return reason is None
 
     def _device_grower_for(self, slot):
         """One DeviceGrower (own heap buffers) per (depth, matrix, slot)."""
@@ -253,7 +324,10 @@ class HistGrower:
             self._device_growers = growers
         dg = growers.get(key)
         if dg is None:
-            dg = self.backend.DeviceGrower(self.state, self.p.max_depth)
+            dg = self.backend.DeviceGrower(
+                self.state, self.p.max_depth,
+                monotone=self.monotone, interaction_sets=self.inter_sets,
+            )
             growers[key] = dg
         return dg
 
@@ -262,30 +336,66 @@ class HistGrower:
         p = self.p
         dg = self._device_grower_for(0)
         dg.state = self.state  # fresh per-tree compact state
-        if tree_mask is not None:
+        level_states = None
+        if p.colsample_bylevel < 1.0 or p.colsample_bynode < 1.0:
+            level_masks, level_states = self._draw_level_masks(tree_mask)
+            dg.mask = level_masks
+        elif tree_mask is not None:
             dg.mask = tree_mask.to(torch.uint8).contiguous()
         splits_np, counts_np, root_np = dg.grow(
             scale, (p.reg_lambda, p.reg_alpha, p.gamma, p.min_child_weight), self.comm
         )
         self.state._level0 = not bool(splits_np[0, 0] > 0)
-        return self._build_tree_from_heap(splits_np, counts_np, root_np, cap)
+        tree, leaf_jobs = self._build_tree_from_heap(splits_np, counts_np, root_np, cap)
+        if level_states is not None and self._live_levels < p.max_depth:
+            # the per-level loop stops drawing once the frontier is empty:
+            # leave the generator where its last live level's draws did
+            self._rng().set_state(level_states[self._live_levels - 1])
+        return tree, leaf_jobs
+
+    def _rng(self):
+        if self.generator is not None:
+            return self.generator
+        if self.device.type == "cuda":
+            index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+            return torch.cuda.default_generators[index]
+        return torch.default_generator
+
+    def _draw_level_masks(self, tree_mask):
+        """Pre-draw the colsample_bylevel / colsample_bynode masks of all
+        max_depth levels in the per-level loop's order (level draw, then the
+        node draw from it), with no host sync. Returns the uint8 [D, f]
+        table (tree mask folded in) and the generator state after each
+        level. A tree that stops early rewinds to the state after its last
+        live level, which is where drawing only that many levels ends."""
+        p = self.p
+        f = self.qm.num_col
+        gen = self._rng()
+        tree_count = self._sample_count(p.colsample_bytree, f)
+        level_count = self._sample_count(p.colsample_bylevel, tree_count)
+        rows, states = [], []
+        for _ in range(p.max_depth):
+            level_mask = self._sample_features(p.colsample_bylevel, tree_mask, tree_count)
+            node_mask = self._sample_features(p.colsample_bynode, level_mask, level_count)
+            rows.append(node_mask)
+            states.append(gen.get_state())
+        return torch.stack(rows).to(torch.uint8).contiguous(), states
 
     def device_async_ok(self):
         """True when a round's independent trees (multiclass / bagging) can
         be enqueued back-to-back via grow_async/grow_finish."""
-        import os as _os
-
         p = self.p
+        # level / node colsample stay sequential: several in-flight trees
+        # sharing one generator cannot reproduce the sequential draw order
+        # (each tree's rewind depends on its own readback)
         return (
             self.comm is None
             and hasattr(self.backend, "DeviceGrower")
-            and _os.environ.get("SMXGB_NO_DEVICE_GROW") != "1"
-            and _os.environ.get("SMXGB_PIPELINE") != "v1"
+            and os.environ.get("SMXGB_NO_DEVICE_GROW") != "1"
+            and os.environ.get("SMXGB_PIPELINE") != "v1"
             and p.grow_policy == "depthwise"
             and p.max_leaves == 0
             and 1 <= p.max_depth <= 10
-            and self.monotone is None
-            and self.inter_sets is None
             and p.colsample_bylevel >= 1.0
             and p.colsample_bynode >= 1.0
         )
@@ -299,11 +409,9 @@ class HistGrower:
         if streams is None:
             streams = {}
             self._streams = streams
-        import os as _os
-
         # SMXGB_CLASS_STREAMS caps concurrent streams (slots share
         # round-robin); default one stream per slot
-        cap = int(_os.environ.get("SMXGB_CLASS_STREAMS", "0") or 0)
+        cap = int(os.environ.get("SMXGB_CLASS_STREAMS", "0") or 0)
         key = slot % cap if cap > 0 else slot
         s = streams.get(key)
         if s is None:
@@ -322,6 +430,7 @@ class HistGrower:
         p = self.p
         qm = self.qm
         n = qm.num_row
+        self.grow_path = "device"
         # per-qm shared caches must exist on the DEFAULT stream before any
         # class stream reads them (class streams only order against the
         # default stream, not each other)
@@ -376,10 +485,15 @@ class HistGrower:
         leaf_jobs = []
         from collections import deque
 
-        # BFS so node numbering matches the per-level path exactly
-        stack = deque([(0, 0, root, 0, cap, G, H)])
+        # this loop sits between one tree's readback and the next tree's
+        # enqueue: unconstrained trees skip the bound bookkeeping
+        monotone = self._monotone_host is not None
+        unbounded = (-float("inf"), float("inf"))
+        # BFS so node numbering matches the per-level path exactly; each
+        # entry carries the node's monotone weight bounds
+        stack = deque([(0, 0, root, 0, cap, G, H, unbounded)])
         while stack:
-            d, i, nid, start, end, g, h = stack.popleft()
+            d, i, nid, start, end, g, h, bounds = stack.popleft()
             hidx = (1 << d) - 1 + i
             gain = float(splits_np[hidx, 0]) if d < D else -1.0
             if d < D and gain > 0.0:
@@ -390,21 +504,30 @@ class HistGrower:
                 lh = float(splits_np[hidx, 5])
                 lc = int(counts_np[hidx, 0])
                 threshold = float(qm._cuts_np[int(qm._cut_ptr_np[feat]) + sbin])
+                if monotone:
+                    wl, wr, lbounds, rbounds = self._child_weights(
+                        feat, bounds[0], bounds[1], lg, lh, g - lg, h - lh
+                    )
+                else:
+                    wl = self._weight(lg, lh)
+                    wr = self._weight(g - lg, h - lh)
+                    lbounds = rbounds = unbounded
                 lid, rid = tree.apply_split(
                     nid, feat, threshold, sbin, dl, gain,
-                    left_value=self._weight(lg, lh) * p.eta,
-                    right_value=self._weight(g - lg, h - lh) * p.eta,
+                    left_value=wl * p.eta,
+                    right_value=wr * p.eta,
                     left_hess=lh,
                     right_hess=h - lh,
                 )
                 mid = start + lc
-                stack.append((d + 1, 2 * i, lid, start, mid, lg, lh))
-                stack.append((d + 1, 2 * i + 1, rid, mid, end, g - lg, h - lh))
+                stack.append((d + 1, 2 * i, lid, start, mid, lg, lh, lbounds))
+                stack.append((d + 1, 2 * i + 1, rid, mid, end, g - lg, h - lh, rbounds))
             else:
                 parity = 0 if d == 0 else d % 2
                 leaf_jobs.append((parity, start, end, float(tree.value[nid])))
+        # levels 0..D-1 that held a node: BFS pops the deepest node last
+        self._live_levels = min(d + 1, D)
         return tree, leaf_jobs
-
 
     # -- depthwise ----------------------------------------------------------
     def _grow_depthwise(self, tree, gh, scale, root_node, tree_mask):
@@ -464,7 +587,8 @@ class HistGrower:
 
             # 2. batched split search
             parent_sums = torch.tensor(
-                [(node.g, node.h) for node in frontier], dtype=torch.float32, device=self.device
+                [node.sum32 if node.sum32 is not None else (node.g, node.h) for node in frontier],
+                dtype=torch.float32, device=self.device,
             )
             node_feature_mask = self._sample_features(p.colsample_bynode, level_mask)
             if any(node.allowed is not None for node in frontier):
@@ -514,15 +638,18 @@ class HistGrower:
                     float(gains[i]), float(lgs[i]), float(lhs[i]),
                 )
                 mid = node.start + counts[i]
+                mirror = node.sum32 is not None
                 next_frontier.append(
                     _Node(lid, 1 - parity, node.start, mid, float(lgs[i]), float(lhs[i]),
-                          depth + 1, lstate[0], lstate[1], lstate[2])
+                          depth + 1, lstate[0], lstate[1], lstate[2],
+                          sum32=(lgs[i], lhs[i]) if mirror else None)
                 )
                 next_frontier.append(
                     _Node(
                         rid, 1 - parity, mid, node.end,
                         node.g - float(lgs[i]), node.h - float(lhs[i]), depth + 1,
                         rstate[0], rstate[1], rstate[2],
+                        sum32=(node.sum32[0] - lgs[i], node.sum32[1] - lhs[i]) if mirror else None,
                     )
                 )
 
@@ -621,20 +748,16 @@ class HistGrower:
         return [(n.parity, n.start, n.end, float(tree.value[n.nid])) for n in nodes.values()]
 
     # -- shared ---------------------------------------------------------------
-    def _apply_split(self, tree, node, feature, bin_idx, default_left, gain, left_g, left_h):
-        """Apply one split: node values honor monotone bounds; returns
-        (lid, rid, left_state, right_state) where each state is
-        (lower, upper, allowed) for the child _Node."""
-        p = self.p
-        GR, HR = node.g - left_g, node.h - left_h
-        cut_base = int(self.qm.cut_ptr[feature])
-        threshold = float(self.qm.cuts[cut_base + bin_idx])
-
-        l_lo, l_hi = node.lower, node.upper
-        r_lo, r_hi = node.lower, node.upper
-        constraint = int(self.monotone[feature]) if self.monotone is not None else 0
-        wl = self._weight(left_g, left_h, node.lower, node.upper)
-        wr = self._weight(GR, HR, node.lower, node.upper)
+    def _child_weights(self, feature, lower, upper, left_g, left_h, right_g, right_h):
+        """Child weights of a split under the parent's monotone weight
+        bounds (lower, upper): a constrained feature pins the children to
+        either side of the midpoint of their clamped weights. Returns
+        (wl, wr, (l_lo, l_hi), (r_lo, r_hi))."""
+        l_lo, l_hi = lower, upper
+        r_lo, r_hi = lower, upper
+        constraint = self._monotone_host[feature] if self._monotone_host is not None else 0
+        wl = self._weight(left_g, left_h, lower, upper)
+        wr = self._weight(right_g, right_h, lower, upper)
         if constraint != 0:
             mid = 0.5 * (wl + wr)
             if constraint > 0:
@@ -644,7 +767,21 @@ class HistGrower:
                 l_lo = max(l_lo, mid)
                 r_hi = min(r_hi, mid)
             wl = self._weight(left_g, left_h, l_lo, l_hi)
-            wr = self._weight(GR, HR, r_lo, r_hi)
+            wr = self._weight(right_g, right_h, r_lo, r_hi)
+        return wl, wr, (l_lo, l_hi), (r_lo, r_hi)
+
+    def _apply_split(self, tree, node, feature, bin_idx, default_left, gain, left_g, left_h):
+        """Apply one split: node values honor monotone bounds; returns
+        (lid, rid, left_state, right_state) where each state is
+        (lower, upper, allowed) for the child _Node."""
+        p = self.p
+        GR, HR = node.g - left_g, node.h - left_h
+        cut_base = int(self.qm.cut_ptr[feature])
+        threshold = float(self.qm.cuts[cut_base + bin_idx])
+
+        wl, wr, (l_lo, l_hi), (r_lo, r_hi) = self._child_weights(
+            feature, node.lower, node.upper, left_g, left_h, GR, HR
+        )
 
         child_allowed = self._interaction_allowed(node.allowed, feature)
 

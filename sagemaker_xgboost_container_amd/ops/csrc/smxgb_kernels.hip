@@ -560,6 +560,46 @@ __global__ void make_root_kernel(LevelNode* root, int* hist_prefix, int* part_pr
   work->part_total = nb;
 }
 
+// Interaction constraints on the device path. A node may only split on
+// features that share a constraint set with every feature split on along
+// its path; that path is known on device only. Allowed sets are bitsets
+// (W = ceil(f/32) words per node, heap-indexed like `nodes`, root all ones):
+//   allowed[child] = allowed[parent] & inter_union[parent's split feature]
+// where inter_union[j] = {j} | (every constraint set containing j), built
+// once on the host. One workgroup per slot of level d >= 1 writes the
+// child's bitset and the level's [k, f] uint8 node mask (level-mask row AND
+// allowed bit) that split_scan_kernel consumes with mask_per_node = 1.
+// Every word and byte of the level is written (dead slots get zeros): the
+// buffers are uninitialised between trees.
+#define NODE_MASK_BLOCK 256
+
+__global__ __launch_bounds__(NODE_MASK_BLOCK) void node_mask_kernel(
+    const LevelNode* __restrict__ par_nodes,       // [k/2] level d-1 nodes
+    const float* __restrict__ par_splits,          // [k/2, 6] level d-1 split records
+    const unsigned* __restrict__ par_allowed,      // [k/2, W]
+    const unsigned* __restrict__ inter_union,      // [f, W]
+    const unsigned char* __restrict__ level_mask,  // [f] row of level d, or null
+    unsigned* __restrict__ allowed,                // [k, W] level d bitsets
+    unsigned char* __restrict__ node_mask,         // [k, f]
+    int k, int f, int W) {
+  const int slot = blockIdx.x;
+  if (slot >= k) return;
+  const int par = slot >> 1;
+  const LevelNode pn = par_nodes[par];
+  const float* sp = par_splits + par * 6;
+  const int feat = (int)sp[1];
+  // same liveness rule as make_level_kernel: the parent holds rows and split
+  const bool live = pn.end > pn.start && sp[0] > 0.0f && feat >= 0 && feat < f;
+  for (int j = threadIdx.x; j < f; j += blockDim.x) {
+    const int w = j >> 5;
+    const unsigned bits =
+        live ? (par_allowed[(long long)par * W + w] & inter_union[(long long)feat * W + w]) : 0u;
+    if ((j & 31) == 0) allowed[(long long)slot * W + w] = bits;
+    const bool on = ((bits >> (j & 31)) & 1u) && (level_mask == nullptr || level_mask[j] != 0);
+    node_mask[(long long)slot * f + j] = on ? 1 : 0;
+  }
+}
+
 __device__ inline int find_slot(const int* __restrict__ prefix, int k, int vb) {
   int lo = 0, hi = k;  // find i with prefix[i] <= vb < prefix[i+1]
   while (lo + 1 < hi) {
@@ -1933,6 +1973,29 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
   }
 }
 
+// One level's interaction-constraint step on its own (the whole-tree
+// enqueue launches the same kernel inline).
+void grow_node_mask(torch::Tensor par_nodes, torch::Tensor par_splits, torch::Tensor par_allowed,
+                    torch::Tensor inter_union, torch::Tensor level_mask, torch::Tensor allowed,
+                    torch::Tensor node_mask, int64_t k, int64_t nfeat) {
+  CHECK_GPU(node_mask);
+  const int64_t W = (nfeat + 31) / 32;
+  const int64_t pk = k >> 1;
+  TORCH_CHECK(k >= 2 && (k & 1) == 0, "grow_node_mask: k must be even and >= 2");
+  TORCH_CHECK(par_nodes.numel() >= pk * 3 && par_splits.numel() >= pk * 6 &&
+                  par_allowed.numel() >= pk * W && inter_union.numel() >= nfeat * W &&
+                  allowed.numel() >= k * W && node_mask.numel() >= k * nfeat &&
+                  (level_mask.numel() == 0 || level_mask.numel() >= nfeat),
+              "grow_node_mask: buffer too small");
+  hipLaunchKernelGGL(node_mask_kernel, dim3((int)k), dim3(NODE_MASK_BLOCK), 0, current_stream(),
+                     (const LevelNode*)par_nodes.data_ptr<int>(), par_splits.data_ptr<float>(),
+                     (const unsigned*)par_allowed.data_ptr<int>(),
+                     (const unsigned*)inter_union.data_ptr<int>(),
+                     level_mask.numel() ? level_mask.data_ptr<unsigned char>() : nullptr,
+                     (unsigned*)allowed.data_ptr<int>(), node_mask.data_ptr<unsigned char>(),
+                     (int)k, (int)nfeat, (int)W);
+}
+
 // Whole-tree enqueue: the entire depthwise grow issued from C++ in one
 // Python call (single-process path; the distributed path keeps the Python
 // per-level loop so torch.distributed can enqueue the allreduce).
@@ -1943,8 +2006,9 @@ void grow_tree_enqueue(
     torch::Tensor nodes, torch::Tensor node_gh, torch::Tensor splits, torch::Tensor counts,
     torch::Tensor hist_f32, torch::Tensor acc, torch::Tensor cands,
     std::vector<torch::Tensor> hp, std::vector<torch::Tensor> pp, torch::Tensor work,
-    torch::Tensor nbins, torch::Tensor feat_mask, torch::Tensor gh_max,
-    int64_t D, int64_t cap, int64_t nfeat, int64_t stride, int64_t n_groups,
+    torch::Tensor nbins, torch::Tensor feat_mask, torch::Tensor monotone,
+    torch::Tensor inter_union, torch::Tensor allowed, torch::Tensor node_mask,
+    torch::Tensor gh_max, int64_t D, int64_t cap, int64_t nfeat, int64_t stride, int64_t n_groups,
     int64_t feats_per_group, int64_t lds_words, int64_t has_missing, int64_t missing_bin,
     int64_t rows_per_block, int64_t max_blocks, int64_t hist_grid, int64_t part_grid,
     double reg_lambda, double reg_alpha, double gamma_, double min_child_weight,
@@ -1954,7 +2018,24 @@ void grow_tree_enqueue(
   const long long slots2 = (long long)nfeat * stride * 2;
   const bool u8 = init_bins.scalar_type() == torch::kUInt8;
   const size_t lds_bytes = (size_t)lds_words * sizeof(unsigned long long);
-  auto mono = torch::Tensor();  // device path excludes monotone constraints
+  // feat_mask: empty, [f] (one tree-wide mask) or [D, f] (row d = level d's
+  // mask, tree/level/node draws already folded in by the host)
+  const unsigned char* mask_base =
+      feat_mask.numel() ? feat_mask.data_ptr<unsigned char>() : nullptr;
+  const long long mask_row = feat_mask.dim() == 2 ? nfeat : 0;
+  const signed char* mono_ptr =
+      monotone.numel() ? (const signed char*)monotone.data_ptr<int8_t>() : nullptr;
+  // interaction constraints: per-node allowed bitsets + [k, f] node masks
+  const bool inter = inter_union.numel() > 0;
+  const long long W = (nfeat + 31) / 32;
+  const long long heap = ((long long)1 << D) - 1;
+  TORCH_CHECK(feat_mask.numel() == 0 || feat_mask.numel() >= (mask_row ? D * nfeat : nfeat),
+              "grow_tree_enqueue: feature mask too small");
+  TORCH_CHECK(monotone.numel() == 0 || monotone.numel() >= nfeat,
+              "grow_tree_enqueue: monotone vector too small");
+  TORCH_CHECK(!inter || (inter_union.numel() >= nfeat * W && allowed.numel() >= heap * W &&
+                         node_mask.numel() >= (heap + 1) / 2 * nfeat),
+              "grow_tree_enqueue: interaction buffers too small");
 
   hipMemsetAsync(counts.data_ptr<int>(), 0, sizeof(int) * 2 * counts.size(0), stream);
 
@@ -2025,12 +2106,25 @@ void grow_tree_enqueue(
       }
     }
 
-    const unsigned char* mask_ptr =
-        feat_mask.numel() ? feat_mask.data_ptr<unsigned char>() : nullptr;
+    const unsigned char* mask_ptr = mask_base ? mask_base + (long long)d * mask_row : nullptr;
+    int mask_per_node = 0;
+    if (inter && d > 0) {
+      const int pbase = (k >> 1) - 1;
+      unsigned* allowed_all = (unsigned*)allowed.data_ptr<int>();
+      hipLaunchKernelGGL(node_mask_kernel, dim3(k), dim3(NODE_MASK_BLOCK), 0, stream,
+                         (const LevelNode*)nodes.data_ptr<int>() + pbase,
+                         splits.data_ptr<float>() + (long long)pbase * 6,
+                         allowed_all + (long long)pbase * W,
+                         (const unsigned*)inter_union.data_ptr<int>(), mask_ptr,
+                         allowed_all + (long long)base * W, node_mask.data_ptr<unsigned char>(), k,
+                         (int)nfeat, (int)W);
+      mask_ptr = node_mask.data_ptr<unsigned char>();
+      mask_per_node = 1;
+    }
     hipLaunchKernelGGL(split_scan_kernel, dim3(k * (int)nfeat), dim3(SPLIT_BLOCK), 0, stream,
-                       hist_d, (const float2*)gh_d, nbins.data_ptr<int>(), mask_ptr, nullptr,
+                       hist_d, (const float2*)gh_d, nbins.data_ptr<int>(), mask_ptr, mono_ptr,
                        (SplitCand*)cands.data_ptr<float>(), k, (int)nfeat, (int)stride,
-                       (int)has_missing, 0, (float)reg_lambda, (float)reg_alpha, (float)gamma_,
+                       (int)has_missing, mask_per_node, (float)reg_lambda, (float)reg_alpha, (float)gamma_,
                        (float)min_child_weight);
     hipLaunchKernelGGL(split_reduce_kernel, dim3(k), dim3(SPLIT_BLOCK), 0, stream,
                        (const SplitCand*)cands.data_ptr<float>(), splits_d, k, (int)nfeat);
@@ -2105,6 +2199,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_convert_level", &grow_convert_level);
   m.def("grow_derive_level", &grow_derive_level);
   m.def("grow_partition_level", &grow_partition_level);
+  m.def("grow_node_mask", &grow_node_mask, "interaction-constraint bitsets + node mask of a level");
   m.def("grow_tree_enqueue", &grow_tree_enqueue, "whole depthwise tree enqueued from one call");
   m.def("partition_compact", &partition_compact, "compacting partition (rows+bins+gh rewrite)");
   m.def("leaf_update_compact", &leaf_update_compact, "leaf scatter from compact row ids");

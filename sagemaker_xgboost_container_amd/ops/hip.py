@@ -672,7 +672,12 @@ class TreeState:
     def update_margins(self, margin_col, leaf_jobs):
         if not leaf_jobs:
             return
-        rows0 = self._rows_init if self._level0 else self._rows[0]
+        # partition_level clears _level0 at the root level without knowing
+        # (no host sync) whether the root split. When it did not, the tree is
+        # one parity-0 leaf over rows that were never copied into _rows[0]:
+        # read the original row ids, not that unwritten buffer.
+        root_leaf = len(leaf_jobs) == 1 and tuple(leaf_jobs[0][:3]) == (0, 0, self.cap)
+        rows0 = self._rows_init if (self._level0 or root_leaf) else self._rows[0]
         packed = []
         blocks_per = []
         first_block = 0
@@ -740,6 +745,21 @@ _GROW_HIST_GRID = int(_os.environ.get("SMXGB_GROW_HIST_GRID", "1536"))
 _GROW_PART_GRID = int(_os.environ.get("SMXGB_GROW_PART_GRID", "4096"))
 
 
+def interaction_union_bitsets(interaction_sets, f):
+    """[f, ceil(f/32)] uint32 table: row j has bit i set when feature i may
+    follow a split on j, i.e. i == j or some constraint set holds both."""
+    W = (f + 31) // 32
+    table = np.zeros((f, W), dtype=np.uint32)
+    for j in range(f):
+        members = {j}
+        for group in interaction_sets:
+            if j in group:
+                members.update(int(i) for i in group if 0 <= int(i) < f)
+        for i in members:
+            table[j, i >> 5] |= np.uint32(1 << (i & 31))
+    return table
+
+
 class DeviceGrower:
     """v3: the whole depthwise tree enqueued with ZERO host syncs; one
     readback (splits + counts heaps) per tree.
@@ -748,9 +768,17 @@ class DeviceGrower:
     choice are computed on device by `make_level`; hist/partition kernels
     walk virtual-block work lists via binary search. Python time between
     enqueues overlaps GPU execution.
+
+    Constraint tables (single-process enqueue only): `mono` is the [f] int8
+    monotone vector the split scan checks directions against; `mask` is
+    empty, a tree-wide [f] mask or a [D, f] table whose row d is level d's
+    mask; `inter_union` (with the `allowed` bitset heap and the `node_mask`
+    level buffer) carries interaction constraints. The latter two exist
+    only when a constraint is set.
     """
 
-    def __init__(self, state, max_depth, feature_mask=None):
+    def __init__(self, state, max_depth, feature_mask=None, monotone=None,
+                 interaction_sets=None):
         assert 1 <= max_depth <= 10, "device grower supports max_depth 1..10"
         self.state = state
         self.qm = state.qm
@@ -789,7 +817,23 @@ class DeviceGrower:
             self.mask = torch.empty(0, dtype=torch.uint8, device=device)
         else:
             self.mask = feature_mask.to(torch.uint8).contiguous()
-        self.mono = torch.empty(0, dtype=torch.int8, device=device)
+        if monotone is None:
+            self.mono = torch.empty(0, dtype=torch.int8, device=device)
+        else:
+            self.mono = monotone.to(device=device, dtype=torch.int8).contiguous()
+        empty_i32 = torch.empty(0, dtype=torch.int32, device=device)
+        self.inter_union = empty_i32
+        self.allowed = empty_i32
+        self.node_mask = torch.empty(0, dtype=torch.uint8, device=device)
+        if interaction_sets:
+            W = (f + 31) // 32
+            self.inter_union = torch.from_numpy(
+                interaction_union_bitsets(interaction_sets, f).view(np.int32)
+            ).to(device)
+            # heap-indexed like `nodes`; the root may use every feature
+            self.allowed = torch.empty((H, W), dtype=torch.int32, device=device)
+            self.allowed[0].fill_(-1)
+            self.node_mask = torch.empty((max_k, f), dtype=torch.uint8, device=device)
         if not hasattr(qm, "_nbins_i32"):
             qm._nbins_i32 = qm.nbins.to(torch.int32).contiguous()
 
@@ -829,7 +873,8 @@ class DeviceGrower:
             st._bins[1], st._gh[1], st._rows[1],
             self.nodes, self.node_gh, self.splits, self.counts,
             self.hist_f32, self.acc, self.cands, self.hp, self.pp, self.work,
-            qm._nbins_i32, self.mask, scale,
+            qm._nbins_i32, self.mask, self.mono,
+            self.inter_union, self.allowed, self.node_mask, scale,
             self.D, st.cap, f, stride, self.n_groups, self.feats_per_group,
             self.lds_words, 1 if qm.has_missing else 0, missing_bin,
             self.rows_per_block, _MAX_BLOCKS_PER_JOB, _GROW_HIST_GRID, _GROW_PART_GRID,
@@ -848,7 +893,8 @@ class DeviceGrower:
     def _graph_eligible(self):
         """hipGraph replay needs stable pointers: full-data state (bins/rows
         alias the matrix; only gh changes round to round — staged) and no
-        per-tree feature mask (its contents change every tree)."""
+        per-tree feature mask (its contents change every tree) or
+        constraint table."""
         st = self.state
         # default OFF: capture/replay of this sequence currently memory-
         # faults on gfx950 (gpurun_out/graph_triage.log); opt in with
@@ -857,6 +903,8 @@ class DeviceGrower:
             _os.environ.get("SMXGB_HIPGRAPH", "0") == "1"
             and st._bins_init is self.qm.bins
             and self.mask.numel() == 0
+            and self.mono.numel() == 0
+            and self.inter_union.numel() == 0
         )
 
     def grow_enqueue(self, scale, split_params):
@@ -959,6 +1007,10 @@ class DeviceGrower:
         if comm is None:
             return self.grow_wait(self.grow_enqueue(scale, split_params))
 
+        # the distributed loop knows neither per-level masks nor
+        # interaction constraints: constrained trees with a communicator
+        # stay on the per-level path
+        assert self.mask.dim() <= 1 and self.inter_union.numel() == 0 and self.mono.numel() == 0
         st = self.state
         qm = self.qm
         f = qm.num_col
