@@ -60,6 +60,8 @@ def launches_per_tree(depth, interaction):
     """Kernel launches + memsets grow_tree_enqueue issues for one tree."""
     per_level = 7  # make_root/make_level, acc memset, hist, convert, scan, reduce, partition
     n = 1 + depth * per_level + (depth - 1)  # counts memset; derive on levels >= 1
+    if os.environ.get("SMXGB_LEAF_UPDATE", "traverse") == "traverse":
+        n -= 1  # full-data trees: the deepest level is not partitioned
     if interaction:
         n += depth - 1  # node-mask kernel on levels >= 1
     return n

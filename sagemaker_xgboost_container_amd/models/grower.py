@@ -336,6 +336,7 @@ class HistGrower:
         p = self.p
         dg = self._device_grower_for(0)
         dg.state = self.state  # fresh per-tree compact state
+        dg.traverse = self._traverse_ok(self.state)
         level_states = None
         if p.colsample_bylevel < 1.0 or p.colsample_bynode < 1.0:
             level_masks, level_states = self._draw_level_masks(tree_mask)
@@ -347,11 +348,28 @@ class HistGrower:
         )
         self.state._level0 = not bool(splits_np[0, 0] > 0)
         tree, leaf_jobs = self._build_tree_from_heap(splits_np, counts_np, root_np, cap)
+        self._bind_traverse(self.state, dg)
         if level_states is not None and self._live_levels < p.max_depth:
             # the per-level loop stops drawing once the frontier is empty:
             # leave the generator where its last live level's draws did
             self._rng().set_state(level_states[self._live_levels - 1])
         return tree, leaf_jobs
+
+    @staticmethod
+    def _traverse_ok(state):
+        """This tree's margins can be updated by traversal (the hip compact
+        state on the full-data path); decided before the tree is enqueued
+        because it also drops the deepest level's partition."""
+        ok = getattr(state, "traverse_ok", None)
+        return bool(ok()) if ok is not None else False
+
+    def _bind_traverse(self, state, dg):
+        """Hand the state what update_margins needs to traverse: the
+        grower's device split heap (valid until its next enqueue) and the
+        heap index of every leaf_jobs entry, in order — the caller may
+        rescale the values (DART) but keeps the order."""
+        if dg.traverse:
+            state._traverse = (dg.splits, self.p.max_depth, self._leaf_heap)
 
     def _rng(self):
         if self.generator is not None:
@@ -454,6 +472,7 @@ class HistGrower:
             tree_mask = self._sample_features(p.colsample_bytree, None)
             dg = self._device_grower_for(slot)
             dg.state = state
+            dg.traverse = self._traverse_ok(state)
             if tree_mask is not None:
                 dg.mask = tree_mask.to(torch.uint8).contiguous()
             ev = dg.grow_enqueue(scale, (p.reg_lambda, p.reg_alpha, p.gamma, p.min_child_weight))
@@ -468,6 +487,7 @@ class HistGrower:
         tree, leaf_jobs = self._build_tree_from_heap(
             splits_np, counts_np, root_np, handle["cap"]
         )
+        self._bind_traverse(state, handle["dg"])
         tree.finalize()
         return tree, leaf_jobs
 
@@ -483,6 +503,11 @@ class HistGrower:
         G, H = float(root_np[0]), float(root_np[1])
         root = tree.add_node(parent=-1, value=self._weight(G, H) * p.eta, sum_hess=H)
         leaf_jobs = []
+        # heap index of each leaf_jobs entry. When margins are updated by
+        # traversal the deepest level is not partitioned, its counts stay
+        # zero and the row ranges of that level's children are placeholders
+        # nobody reads; the heap indices are what that update uses.
+        leaf_heap = []
         from collections import deque
 
         # this loop sits between one tree's readback and the next tree's
@@ -525,6 +550,8 @@ class HistGrower:
             else:
                 parity = 0 if d == 0 else d % 2
                 leaf_jobs.append((parity, start, end, float(tree.value[nid])))
+                leaf_heap.append(hidx)
+        self._leaf_heap = leaf_heap
         # levels 0..D-1 that held a node: BFS pops the deepest node last
         self._live_levels = min(d + 1, D)
         return tree, leaf_jobs

@@ -441,6 +441,104 @@ __global__ __launch_bounds__(HIST_BLOCK) void leaf_update_compact_kernel(
   }
 }
 
+// Margin update by streaming traversal (full-data device-grown trees). Every
+// row of the ORIGINAL bin matrix walks the finished tree's split heap with
+// the partition's predicate and adds its leaf's value to its own margin
+// cell: one coalesced pass over bins and margin, no row ids, no scatter and
+// no partition of the deepest level. The add is the same float32 add of the
+// same host-computed value the scatter does, so margins stay bit-identical.
+//
+// splits: the grower's [2^D - 1, 6] heap (gain, feature, split_bin,
+// default_left, lg, lh); a node with gain <= 0 is a leaf, as in
+// make_level_kernel. values: [2^(D+1) - 1] leaf values by heap index. Both
+// are staged in LDS once per block (split records packed to two ints), so
+// the row loop touches no float record.
+//
+// STAGED (u8 bins, nfeat % 4 == 0): each 256-row tile is copied into LDS
+// with 16-B coalesced loads and traversed from there — a thread-per-row read
+// of nfeat-byte rows would fetch with an nfeat-byte lane stride. The LDS
+// byte reads have a lane stride of nfeat/4 dwords: conflict-free when that
+// is odd (28 features -> 7). Otherwise rows are read in place.
+#define TRAV_TILE 256
+
+__device__ inline int traverse_step(int2 rec, int b, int missing_bin) {
+  const bool left = (b == missing_bin) ? ((rec.y & 1) != 0) : (b <= (rec.y >> 1));
+  return left ? 1 : 2;
+}
+
+template <typename BinT, bool STAGED>
+__global__ __launch_bounds__(HIST_BLOCK) void leaf_update_traverse_kernel(
+    const BinT* __restrict__ bins, const float* __restrict__ splits,
+    const float* __restrict__ values, float* __restrict__ margin, long long n, int nfeat,
+    int D, int missing_bin, long long col_stride) {
+  extern __shared__ __align__(16) unsigned char trav_smem[];
+  const int heap = (1 << D) - 1;
+  const int nvals = 2 * heap + 1;
+  int2* lnode = reinterpret_cast<int2*>(trav_smem);      // [heap]
+  float* lval = reinterpret_cast<float*>(lnode + heap);  // [nvals]
+  for (int h = threadIdx.x; h < heap; h += blockDim.x) {
+    const float* sp = splits + h * 6;
+    int2 rec = make_int2(-1, 0);
+    // slots no row reaches hold whatever the split scan left there: keep
+    // any feature outside the matrix from ever forming an address
+    if (sp[0] > 0.0f && sp[1] >= 0.0f && sp[1] < (float)nfeat) {
+      rec.x = (int)sp[1];
+      rec.y = ((int)sp[2] << 1) | (sp[3] > 0.5f ? 1 : 0);
+    }
+    lnode[h] = rec;
+  }
+  for (int h = threadIdx.x; h < nvals; h += blockDim.x) lval[h] = values[h];
+  __syncthreads();
+
+  if (STAGED) {
+    // tables take 16 * heap + 4 bytes; the tile starts on the next 16
+    unsigned* ltile = reinterpret_cast<unsigned*>(trav_smem + 16 * (heap + 1));
+    const unsigned char* lbytes = reinterpret_cast<const unsigned char*>(ltile);
+    const int nd = nfeat >> 2;
+    const long long ntiles = (n + TRAV_TILE - 1) / TRAV_TILE;
+    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+      const long long row0 = t * TRAV_TILE;
+      const int tile_n = (int)min((long long)TRAV_TILE, n - row0);
+      const long long r = row0 + threadIdx.x;
+      float m = 0.f;
+      if ((int)threadIdx.x < tile_n) m = margin[r * col_stride];  // in flight during the copy
+      const unsigned char* src = reinterpret_cast<const unsigned char*>(bins) + row0 * nfeat;
+      if (tile_n == TRAV_TILE) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* l4 = reinterpret_cast<uint4*>(ltile);
+        for (int u = threadIdx.x; u < (TRAV_TILE >> 2) * nd; u += blockDim.x) l4[u] = s4[u];
+      } else {
+        const unsigned* s1 = reinterpret_cast<const unsigned*>(src);
+        for (int u = threadIdx.x; u < tile_n * nd; u += blockDim.x) ltile[u] = s1[u];
+      }
+      __syncthreads();
+      if ((int)threadIdx.x < tile_n) {
+        const unsigned char* row = lbytes + (int)threadIdx.x * nfeat;
+        int h = 0;
+        for (int d = 0; d < D; ++d) {
+          const int2 rec = lnode[h];
+          if (rec.x < 0) break;
+          h = 2 * h + traverse_step(rec, (int)row[rec.x], missing_bin);
+        }
+        margin[r * col_stride] = m + lval[h];
+      }
+      __syncthreads();
+    }
+  } else {
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += step) {
+      const BinT* row = bins + r * nfeat;
+      int h = 0;
+      for (int d = 0; d < D; ++d) {
+        const int2 rec = lnode[h];
+        if (rec.x < 0) break;
+        h = 2 * h + traverse_step(rec, (int)row[rec.x], missing_bin);
+      }
+      margin[r * col_stride] += lval[h];
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // DEVICE-AUTONOMOUS depthwise grow (v3)
 //
@@ -1800,6 +1898,69 @@ void leaf_update_compact(torch::Tensor rows0, torch::Tensor rows1, torch::Tensor
                      (const LeafJob*)jobs.data_ptr<int>(), block_job.data_ptr<int>(), col_stride);
 }
 
+template <typename BinT>
+static void launch_leaf_traverse(bool staged, int grid, size_t lds, hipStream_t stream,
+                                 const BinT* bins, const float* splits, const float* values,
+                                 float* margin, long long n, int nfeat, int D, int missing_bin,
+                                 long long col_stride) {
+  if (staged) {
+    hipLaunchKernelGGL((leaf_update_traverse_kernel<BinT, true>), dim3(grid), dim3(HIST_BLOCK),
+                       lds, stream, bins, splits, values, margin, n, nfeat, D, missing_bin,
+                       col_stride);
+  } else {
+    hipLaunchKernelGGL((leaf_update_traverse_kernel<BinT, false>), dim3(grid), dim3(HIST_BLOCK),
+                       lds, stream, bins, splits, values, margin, n, nfeat, D, missing_bin,
+                       col_stride);
+  }
+}
+
+// margin[r * col_stride] += values[leaf(r)] for every row of the bin matrix
+void leaf_update_traverse(torch::Tensor bins, torch::Tensor splits, torch::Tensor values,
+                          torch::Tensor margin_base, int64_t D, int64_t missing_bin,
+                          int64_t col_stride) {
+  CHECK_GPU(bins);
+  CHECK_GPU(splits);
+  CHECK_GPU(values);
+  CHECK_GPU(margin_base);
+  TORCH_CHECK(D >= 1 && D <= 10, "leaf_update_traverse: depth must be 1..10");
+  TORCH_CHECK(bins.dim() == 2 && bins.is_contiguous(), "leaf_update_traverse: bins must be [n, f]");
+  const long long n = bins.size(0);
+  const int nfeat = (int)bins.size(1);
+  const long long heap = ((long long)1 << D) - 1;
+  TORCH_CHECK(splits.scalar_type() == torch::kFloat32 && splits.is_contiguous() &&
+                  splits.numel() >= heap * 6,
+              "leaf_update_traverse: split heap too small");
+  TORCH_CHECK(values.scalar_type() == torch::kFloat32 && values.is_contiguous() &&
+                  values.numel() >= 2 * heap + 1,
+              "leaf_update_traverse: value table too small");
+  TORCH_CHECK(margin_base.scalar_type() == torch::kFloat32 && margin_base.dim() == 1 &&
+                  margin_base.size(0) == n && margin_base.stride(0) == col_stride,
+              "leaf_update_traverse: margin column does not match the bin matrix");
+  if (n == 0) return;
+  auto stream = current_stream();
+  const size_t tables = (size_t)16 * (heap + 1);
+  if (bins.scalar_type() == torch::kUInt8) {
+    const unsigned char* ptr = bins.data_ptr<unsigned char>();
+    const size_t tile = (size_t)TRAV_TILE * nfeat;
+    const bool staged = (nfeat & 3) == 0 && tables + tile <= 48 * 1024 &&
+                        (reinterpret_cast<uintptr_t>(ptr) & 15) == 0;
+    const long long blocks =
+        staged ? (n + TRAV_TILE - 1) / TRAV_TILE : (n + HIST_BLOCK - 1) / HIST_BLOCK;
+    launch_leaf_traverse<unsigned char>(staged, (int)std::min<long long>(blocks, 2048),
+                                        tables + (staged ? tile : 0), stream, ptr,
+                                        splits.data_ptr<float>(), values.data_ptr<float>(),
+                                        margin_base.data_ptr<float>(), n, nfeat, (int)D,
+                                        (int)missing_bin, col_stride);
+  } else {
+    TORCH_CHECK(bins.scalar_type() == torch::kInt16, "leaf_update_traverse: bins must be u8 or i16");
+    const long long blocks = (n + HIST_BLOCK - 1) / HIST_BLOCK;
+    launch_leaf_traverse<short>(false, (int)std::min<long long>(blocks, 2048), tables, stream,
+                                bins.data_ptr<short>(), splits.data_ptr<float>(),
+                                values.data_ptr<float>(), margin_base.data_ptr<float>(), n, nfeat,
+                                (int)D, (int)missing_bin, col_stride);
+  }
+}
+
 void grow_make_root(torch::Tensor nodes, torch::Tensor hist_prefix, torch::Tensor part_prefix,
                     torch::Tensor work, int64_t cap, int64_t rows_per_block, int64_t max_blocks) {
   hipLaunchKernelGGL(make_root_kernel, dim3(1), dim3(1), 0, current_stream(),
@@ -2012,7 +2173,7 @@ void grow_tree_enqueue(
     int64_t feats_per_group, int64_t lds_words, int64_t has_missing, int64_t missing_bin,
     int64_t rows_per_block, int64_t max_blocks, int64_t hist_grid, int64_t part_grid,
     double reg_lambda, double reg_alpha, double gamma_, double min_child_weight,
-    int64_t hist_block) {
+    int64_t hist_block, int64_t skip_last_partition) {
   CHECK_GPU(init_bins);
   auto stream = current_stream();
   const long long slots2 = (long long)nfeat * stride * 2;
@@ -2130,6 +2291,9 @@ void grow_tree_enqueue(
                        (const SplitCand*)cands.data_ptr<float>(), splits_d, k, (int)nfeat);
 
     const int copy_payload = d < (int)D - 1 ? 1 : 0;  // last level: rows+counts only
+    // margins updated by traversal: nothing consumes the deepest level's
+    // row ids and counts, so that level is not partitioned at all
+    if (!copy_payload && skip_last_partition) continue;
     if (u8) {
       if (!launch_part_lds((int)part_grid, stream, (const unsigned char*)src_bins, src_gh,
                            src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d, pp_d,
@@ -2203,6 +2367,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_tree_enqueue", &grow_tree_enqueue, "whole depthwise tree enqueued from one call");
   m.def("partition_compact", &partition_compact, "compacting partition (rows+bins+gh rewrite)");
   m.def("leaf_update_compact", &leaf_update_compact, "leaf scatter from compact row ids");
+  m.def("leaf_update_traverse", &leaf_update_traverse,
+        "margin update by streaming traversal of the split heap");
   m.def("leaf_update", &leaf_update, "batched leaf value scatter into margins");
   m.def("predict_forest", &predict_forest, "batched dense forest traversal");
   m.def("grad_fused", &grad_fused, "one-pass gradient + absmax partials");

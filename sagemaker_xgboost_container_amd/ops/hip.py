@@ -609,6 +609,19 @@ class TreeState:
         self._gh = [cache[2], cache[3]]
         self._rows = [cache[4], cache[5]]
         self._level0 = True  # parity-0 source is still the original matrix
+        # (split heap, depth, leaf heap indices) of a device-grown tree whose
+        # margins are updated by traversal; None selects the leaf scatter
+        self._traverse = None
+
+    def traverse_ok(self):
+        """Margins of this tree can be updated by streaming the original
+        bin matrix through the finished tree: full-data state only (a
+        subsampled tree must leave the rows it did not see untouched).
+        SMXGB_LEAF_UPDATE=scatter keeps the row-id scatter for A/B runs."""
+        mode = _os.environ.get("SMXGB_LEAF_UPDATE", "traverse")
+        if mode not in ("traverse", "scatter"):
+            raise ValueError(f"SMXGB_LEAF_UPDATE must be 'traverse' or 'scatter', got {mode!r}")
+        return mode == "traverse" and self._bins_init is self.qm.bins
 
     def _src(self, parity):
         if parity == 0 and self._level0:
@@ -671,6 +684,23 @@ class TreeState:
 
     def update_margins(self, margin_col, leaf_jobs):
         if not leaf_jobs:
+            return
+        if self._traverse is not None:
+            # the value table is built HERE, from the values the caller
+            # passes: DART rescales them after the tree was grown. Leaf i of
+            # leaf_jobs sits at heap index leaf_heap[i]; its row range is a
+            # placeholder (the deepest level was never partitioned). A root
+            # that did not split is just the depth-0 leaf.
+            splits, depth, leaf_heap = self._traverse
+            assert len(leaf_heap) == len(leaf_jobs)
+            table = np.zeros((2 << depth) - 1, dtype=np.float32)
+            table[leaf_heap] = np.asarray([job[3] for job in leaf_jobs], dtype=np.float32)
+            values = torch.from_numpy(table).to(margin_col.device, non_blocking=True)
+            qm = self.qm
+            missing_bin = qm.stride - 1 if qm.has_missing else -1
+            _K.leaf_update_traverse(
+                qm.bins, splits, values, margin_col, depth, missing_bin, margin_col.stride(0)
+            )
             return
         # partition_level clears _level0 at the root level without knowing
         # (no host sync) whether the root split. When it did not, the tree is
@@ -783,6 +813,10 @@ class DeviceGrower:
         self.state = state
         self.qm = state.qm
         self.D = max_depth
+        # set per tree by the grower (TreeState.traverse_ok()): margins are
+        # updated by traversal, so the deepest level is not partitioned. Off
+        # for direct users, whose leaf scatter needs that level's row ids.
+        self.traverse = False
         # virtual-block granularity adapts to the tree's row count: small
         # trees (multiclass class-trees, small data) need more blocks in
         # flight to fill 256 CUs — measured 141 -> 178 r/s on Covertype-
@@ -879,6 +913,7 @@ class DeviceGrower:
             self.lds_words, 1 if qm.has_missing else 0, missing_bin,
             self.rows_per_block, _MAX_BLOCKS_PER_JOB, _GROW_HIST_GRID, _GROW_PART_GRID,
             reg_lambda, reg_alpha, gamma, mcw, self.hist_block,
+            1 if self.traverse else 0,
         )
         if not hasattr(self, "_pinned"):
             self._pinned = (
@@ -928,7 +963,7 @@ class DeviceGrower:
             # captured body must be allocation-free — see _enqueue_body)
             if rootsum is None:
                 rootsum = st._gh_init.to(torch.float64).sum(0)
-            key = (st.cap, split_params)
+            key = (st.cap, split_params, self.traverse)
             dbg = _os.environ.get("SMXGB_GRAPH_DEBUG") == "1"
 
             def _d(msg):
@@ -1128,6 +1163,10 @@ class DeviceGrower:
                 1 if qm.has_missing else 0, 0, reg_lambda, reg_alpha, gamma, mcw,
             )
 
+            if self.traverse and d == self.D - 1:
+                # margins updated by traversal: nothing reads the deepest
+                # level's row ids or counts
+                continue
             dst = 1 - d % 2
             _K.grow_partition_level(
                 src_bins, src_gh, src_rows, st._bins[dst], st._gh[dst], st._rows[dst],
