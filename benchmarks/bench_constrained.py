@@ -62,6 +62,8 @@ def launches_per_tree(depth, interaction):
     n = 1 + depth * per_level + (depth - 1)  # counts memset; derive on levels >= 1
     if os.environ.get("SMXGB_LEAF_UPDATE", "traverse") == "traverse":
         n -= 1  # full-data trees: the deepest level is not partitioned
+        if depth >= 2 and os.environ.get("SMXGB_DEEPEST_HIST", "filter") != "partition":
+            n -= 1  # nor is the level above it: the deepest histogram filters
     if interaction:
         n += depth - 1  # node-mask kernel on levels >= 1
     return n

@@ -504,9 +504,11 @@ class HistGrower:
         root = tree.add_node(parent=-1, value=self._weight(G, H) * p.eta, sum_hess=H)
         leaf_jobs = []
         # heap index of each leaf_jobs entry. When margins are updated by
-        # traversal the deepest level is not partitioned, its counts stay
-        # zero and the row ranges of that level's children are placeholders
-        # nobody reads; the heap indices are what that update uses.
+        # traversal the deepest level is not partitioned (nor, with the
+        # filtered deepest histogram, the level above it): the counts of
+        # levels D-2 and D-1 stay zero and the row ranges derived from them
+        # below are placeholders nobody reads; the heap indices are what
+        # that update uses.
         leaf_heap = []
         from collections import deque
 

@@ -572,6 +572,12 @@ struct LevelWork {
 // Single-block kernel: build level d+1's node table from level d's
 // splits/counts, choose build children (smaller hessian), compute
 // per-slot virtual-block counts + exclusive prefixes for hist & partition.
+//
+// filtered != 0: level d was NOT partitioned (its counts are zero). Both
+// children of a live parent get the parent's own [start, end); the build
+// child's histogram launch streams that range and keeps the rows the
+// parent's split sends to its side (hist_device_kernel, FILTER), so its
+// block count comes from the parent's row count.
 __global__ __launch_bounds__(GROW_MAX_SLOTS) void make_level_kernel(
     const LevelNode* __restrict__ cur,    // [k] level d nodes
     const float* __restrict__ splits,     // [k, 6] level d split records
@@ -581,7 +587,7 @@ __global__ __launch_bounds__(GROW_MAX_SLOTS) void make_level_kernel(
     float* __restrict__ nxt_gh,           // [2k, 2]
     int* __restrict__ hist_prefix,        // [2k + 1]
     int* __restrict__ part_prefix,        // [2k + 1]
-    LevelWork* __restrict__ work, int k, int rows_per_block, int max_blocks) {
+    LevelWork* __restrict__ work, int k, int rows_per_block, int max_blocks, int filtered) {
   __shared__ int h_counts[2 * GROW_MAX_SLOTS];
   __shared__ int p_counts[2 * GROW_MAX_SLOTS];
   const int tid = threadIdx.x;
@@ -592,10 +598,10 @@ __global__ __launch_bounds__(GROW_MAX_SLOTS) void make_level_kernel(
     LevelNode lft = {0, 0, 0}, rgt = {0, 0, 0};
     float lg = 0.f, lh = 0.f, rg = 0.f, rh = 0.f;
     if (node.end > node.start && sp[0] > 0.0f) {
-      const int lc = counts[i * 2];
+      const int lc = filtered ? node.end - node.start : counts[i * 2];
       lft.start = node.start;
       lft.end = node.start + lc;
-      rgt.start = lft.end;
+      rgt.start = filtered ? node.start : lft.end;
       rgt.end = node.end;
       lg = sp[4];
       lh = sp[5];
@@ -715,14 +721,145 @@ __device__ inline int find_slot(const int* __restrict__ prefix, int k, int vb) {
 // BLOCK=256 pairs with grouped 56 KB slabs (2 blocks/CU); BLOCK=512 runs a
 // SINGLE full-feature slab (up to ~158 KB, 1 block/CU — the same 8 waves,
 // but bins/gh stream ONCE per row instead of once per feature group).
-template <typename BinT, int BLOCK>
+//
+// FILTER (the deepest level when the level above it was not partitioned):
+// nodes[slot] holds the PARENT's row range and par_splits the parent
+// level's [k/2, 6] split records. Slot s accumulates only the rows the
+// partition's own predicate would have moved to side (s & 1) of parent
+// s >> 1, classified by one byte load per row. The same rows contribute the
+// same fixed-point values as after a partition, so the sums are bit-equal.
+//   PREDICATE: rows stay lane-consecutive; bin loads and atomics of the
+//     other rows are predicated off. Every LDS atomic instruction still
+//     issues with about half its lanes idle.
+//   COMPACT: each wave classifies tiles of 64 consecutive rows, ballots and
+//     queues the kept row indices in its own LDS queue behind the slab; once
+//     4 x 64 rows wait they go through the 4-rows-in-flight loop with full
+//     lanes. The wave walks the block-strided loop as a whole, so the
+//     classify loads stay coalesced and the queued rows stay close together.
+//     Needs HIST_QUEUE_ROWS ints per wave behind the slab (queue_ofs, in
+//     u64 words); the host picks it only where that does not cost occupancy.
+#define HIST_FILTER_OFF 0
+#define HIST_FILTER_PREDICATE 1
+#define HIST_FILTER_COMPACT 2
+#define HIST_ROWS_IN_FLIGHT 4
+// a wave classifies this many 64-row tiles per step, their byte loads all in
+// flight together: with one load per step the 8 waves of a CU wait out the
+// memory latency once per 64 rows
+#define HIST_CLASSIFY_TILES 4
+// one drain (4 x 64 rows) plus what a step can add to a queue just short of it
+#define HIST_QUEUE_ROWS (HIST_ROWS_IN_FLIGHT * 64 + HIST_CLASSIFY_TILES * 64)
+static_assert(HIST_CLASSIFY_TILES <= HIST_ROWS_IN_FLIGHT,
+              "one drain per step must bring the queue back under a drain's worth");
+
+__device__ inline bool hist_row_kept(int b, int missing_bin, int split_bin, bool default_left,
+                                     bool want_left) {
+  const bool left = (b == missing_bin) ? default_left : (b <= split_bin);
+  return left == want_left;
+}
+
+// 4 bins per dword load (rows are 4-aligned when nfeat % 4 == 0);
+// HIST_ROWS_IN_FLIGHT rows per lane in flight so the gathers overlap
+template <typename BinT, bool PRED>
+__device__ inline void hist_add_rows_vec4(unsigned long long* lhist, int hofs,
+                                          const BinT* __restrict__ bins_c,
+                                          const float2* __restrict__ gh_c,
+                                          const long long (&ru)[HIST_ROWS_IN_FLIGHT],
+                                          const bool (&keep)[HIST_ROWS_IN_FLIGHT], int nfeat,
+                                          int fg_start, int nd, int stride, float scale_g,
+                                          float scale_h) {
+  constexpr int HROWS = HIST_ROWS_IN_FLIGHT;
+  unsigned long long gf[HROWS], hf[HROWS];
+  const uchar4* rp[HROWS];
+  #pragma unroll
+  for (int u = 0; u < HROWS; ++u) {
+    const float2 gp = gh_c[ru[u]];
+    gf[u] = (unsigned long long)(long long)llrintf(gp.x * scale_g);
+    hf[u] = (unsigned long long)(long long)llrintf(gp.y * scale_h);
+    rp[u] = reinterpret_cast<const uchar4*>(bins_c + ru[u] * nfeat + fg_start);
+  }
+  #pragma unroll 2
+  for (int f4 = 0; f4 < nd; ++f4) {
+    const int base = (f4 << 2) * stride;
+    uchar4 b4[HROWS];
+    #pragma unroll
+    for (int u = 0; u < HROWS; ++u) {
+      if (!PRED || keep[u]) b4[u] = rp[u][f4];
+    }
+    #pragma unroll
+    for (int u = 0; u < HROWS; ++u) {
+      if (PRED && !keep[u]) continue;
+      const int s0 = lds_pad_slot(base + (int)b4[u].x);
+      const int s1 = lds_pad_slot(base + stride + (int)b4[u].y);
+      const int s2 = lds_pad_slot(base + 2 * stride + (int)b4[u].z);
+      const int s3 = lds_pad_slot(base + 3 * stride + (int)b4[u].w);
+      atomicAdd(&lhist[s0], gf[u]);
+      atomicAdd(&lhist[hofs + s0], hf[u]);
+      atomicAdd(&lhist[s1], gf[u]);
+      atomicAdd(&lhist[hofs + s1], hf[u]);
+      atomicAdd(&lhist[s2], gf[u]);
+      atomicAdd(&lhist[hofs + s2], hf[u]);
+      atomicAdd(&lhist[s3], gf[u]);
+      atomicAdd(&lhist[hofs + s3], hf[u]);
+    }
+  }
+}
+
+// one row per lane: the tail of a range, and every row of a scalar-loop slab
+template <typename BinT>
+__device__ inline void hist_add_row(unsigned long long* lhist, int hofs,
+                                    const BinT* __restrict__ bins_c,
+                                    const float2* __restrict__ gh_c, long long r, bool vec4,
+                                    int nfeat, int fg_start, int nf_group, int stride,
+                                    float scale_g, float scale_h) {
+  const float2 gp = gh_c[r];
+  const unsigned long long gfix = (unsigned long long)(long long)llrintf(gp.x * scale_g);
+  const unsigned long long hfix = (unsigned long long)(long long)llrintf(gp.y * scale_h);
+  const BinT* rp = bins_c + r * nfeat + fg_start;
+  if (vec4) {
+    const uchar4* rp4 = reinterpret_cast<const uchar4*>(rp);
+    #pragma unroll 2
+    for (int f4 = 0; f4 < (nf_group >> 2); ++f4) {
+      const uchar4 b4 = rp4[f4];
+      const int base = (f4 << 2) * stride;
+      const int s0 = lds_pad_slot(base + (int)b4.x);
+      const int s1 = lds_pad_slot(base + stride + (int)b4.y);
+      const int s2 = lds_pad_slot(base + 2 * stride + (int)b4.z);
+      const int s3 = lds_pad_slot(base + 3 * stride + (int)b4.w);
+      atomicAdd(&lhist[s0], gfix);
+      atomicAdd(&lhist[hofs + s0], hfix);
+      atomicAdd(&lhist[s1], gfix);
+      atomicAdd(&lhist[hofs + s1], hfix);
+      atomicAdd(&lhist[s2], gfix);
+      atomicAdd(&lhist[hofs + s2], hfix);
+      atomicAdd(&lhist[s3], gfix);
+      atomicAdd(&lhist[hofs + s3], hfix);
+    }
+    return;
+  }
+  #pragma unroll 4
+  for (int f = 0; f < nf_group; ++f) {
+    const int slot2 = lds_pad_slot(f * stride + (int)rp[f]);
+    atomicAdd(&lhist[slot2], gfix);
+    atomicAdd(&lhist[hofs + slot2], hfix);
+  }
+}
+
+// queue writes of some lanes are read by other lanes of the same wave
+__device__ inline void hist_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <typename BinT, int BLOCK, int FILTER>
 __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
     const BinT* __restrict__ bins_c, const float2* __restrict__ gh_c,
     const LevelNode* __restrict__ nodes, const int* __restrict__ hist_prefix,
     const LevelWork* __restrict__ work, unsigned long long* __restrict__ out,
     int k, int nfeat, int stride, int n_groups, int feats_per_group,
-    const float* __restrict__ gh_max, int rows_per_block, int slot_lo, int slot_hi) {
+    const float* __restrict__ gh_max, int rows_per_block, int slot_lo, int slot_hi,
+    const float* __restrict__ par_splits, int missing_bin, int queue_ofs) {
   extern __shared__ unsigned long long lhist[];
+  constexpr int HROWS = HIST_ROWS_IN_FLIGHT;
   const float scale_g = 8589934592.0f / fmaxf(gh_max[0], 1e-30f);
   const float scale_h = 8589934592.0f / fmaxf(gh_max[1], 1e-30f);
   const int total = work->hist_total * n_groups;
@@ -735,6 +872,18 @@ __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
     const int chunk = hvb - hist_prefix[slot];
     const int nb = hist_prefix[slot + 1] - hist_prefix[slot];
     const LevelNode node = nodes[slot];
+    int flt_feat = 0, flt_bin = 0;
+    bool flt_dl = false;
+    const bool flt_left = (slot & 1) == 0;
+    if (FILTER != HIST_FILTER_OFF) {
+      const float* sp = par_splits + (slot >> 1) * 6;
+      flt_feat = (int)sp[1];
+      flt_bin = (int)sp[2];
+      flt_dl = sp[3] > 0.5f;
+      // a slot has blocks only under a live parent, whose feature is valid;
+      // never form an address from anything else
+      if (flt_feat < 0 || flt_feat >= nfeat) continue;
+    }
     const int fg_start = fg * feats_per_group;
     const int nf_group = min(feats_per_group, nfeat - fg_start);
     const int lds_words = nf_group * stride * 2;
@@ -747,78 +896,92 @@ __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
     const long long step = (long long)nb * blockDim.x;
     const bool vec4 = sizeof(BinT) == 1 && (nf_group & 3) == 0 && (nfeat & 3) == 0 &&
                       (fg_start & 3) == 0;
+    const int nd = nf_group >> 2;
     long long r = node.start + (long long)chunk * blockDim.x + threadIdx.x;
-    if (vec4) {
-      // 4 bins per dword load (rows are 4-aligned when nfeat % 4 == 0);
-      // HROWS rows in flight per iteration so the gathers overlap
-      constexpr int HROWS = 4;
-      const int nd = nf_group >> 2;
-      for (; r + (HROWS - 1) * step < node.end; r += HROWS * step) {
-        unsigned long long gf[HROWS], hf[HROWS];
-        const uchar4* rp[HROWS];
+    if (FILTER == HIST_FILTER_COMPACT) {
+      int* queue =
+          reinterpret_cast<int*>(lhist + queue_ofs) + (threadIdx.x >> 6) * HIST_QUEUE_ROWS;
+      const int lane = threadIdx.x & 63;
+      const bool all_true[HROWS] = {true, true, true, true};
+      int qn = 0;  // the same in every lane: it only adds ballot counts
+      constexpr int CT = HIST_CLASSIFY_TILES;
+      for (long long r0 = r - lane; r0 < node.end; r0 += CT * step) {
+        int b[CT];
+        #pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          const long long rr = r0 + c * step + lane;
+          b[c] = rr < node.end ? (int)bins_c[rr * nfeat + flt_feat] : 0;
+        }
+        #pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          const long long rr = r0 + c * step + lane;
+          const bool kept =
+              rr < node.end && hist_row_kept(b[c], missing_bin, flt_bin, flt_dl, flt_left);
+          const unsigned long long m = __ballot(kept);
+          if (kept) queue[qn + __popcll(m & ((1ull << lane) - 1ull))] = (int)rr;
+          qn += __popcll(m);
+        }
+        hist_wave_sync();
+        // at most 4 x 64 - 1 rows waited and CT x 64 came: one drain leaves
+        // fewer than 4 x 64 again
+        if (qn >= HROWS * 64) {
+          qn -= HROWS * 64;  // the newest rows: nothing has to move down
+          long long ru[HROWS];
+          #pragma unroll
+          for (int u = 0; u < HROWS; ++u) ru[u] = queue[qn + u * 64 + lane];
+          if (vec4) {
+            hist_add_rows_vec4<BinT, false>(lhist, hofs, bins_c, gh_c, ru, all_true, nfeat,
+                                            fg_start, nd, stride, scale_g, scale_h);
+          } else {
+            #pragma unroll
+            for (int u = 0; u < HROWS; ++u)
+              hist_add_row<BinT>(lhist, hofs, bins_c, gh_c, ru[u], false, nfeat, fg_start,
+                                 nf_group, stride, scale_g, scale_h);
+          }
+          hist_wave_sync();
+        }
+      }
+      // what is left (fewer than 4 x 64 rows) goes through the same loop;
+      // only its last 64-row batch runs with idle lanes
+      if (vec4 && qn > 0) {
+        long long ru[HROWS];
+        bool keep[HROWS];
         #pragma unroll
         for (int u = 0; u < HROWS; ++u) {
-          const long long ru = r + u * step;
-          const float2 gp = gh_c[ru];
-          gf[u] = (unsigned long long)(long long)llrintf(gp.x * scale_g);
-          hf[u] = (unsigned long long)(long long)llrintf(gp.y * scale_h);
-          rp[u] = reinterpret_cast<const uchar4*>(bins_c + ru * nfeat + fg_start);
+          keep[u] = u * 64 + lane < qn;
+          ru[u] = keep[u] ? queue[u * 64 + lane] : node.start;
         }
-        #pragma unroll 2
-        for (int f4 = 0; f4 < nd; ++f4) {
-          const int base = (f4 << 2) * stride;
-          uchar4 b4[HROWS];
-          #pragma unroll
-          for (int u = 0; u < HROWS; ++u) b4[u] = rp[u][f4];
+        hist_add_rows_vec4<BinT, true>(lhist, hofs, bins_c, gh_c, ru, keep, nfeat, fg_start, nd,
+                                       stride, scale_g, scale_h);
+      } else {
+        for (int i = lane; i < qn; i += 64)
+          hist_add_row<BinT>(lhist, hofs, bins_c, gh_c, (long long)queue[i], false, nfeat,
+                             fg_start, nf_group, stride, scale_g, scale_h);
+      }
+    } else {
+      if (vec4) {
+        for (; r + (HROWS - 1) * step < node.end; r += HROWS * step) {
+          long long ru[HROWS];
+          bool keep[HROWS];
           #pragma unroll
           for (int u = 0; u < HROWS; ++u) {
-            const int s0 = lds_pad_slot(base + (int)b4[u].x);
-            const int s1 = lds_pad_slot(base + stride + (int)b4[u].y);
-            const int s2 = lds_pad_slot(base + 2 * stride + (int)b4[u].z);
-            const int s3 = lds_pad_slot(base + 3 * stride + (int)b4[u].w);
-            atomicAdd(&lhist[s0], gf[u]);
-            atomicAdd(&lhist[hofs + s0], hf[u]);
-            atomicAdd(&lhist[s1], gf[u]);
-            atomicAdd(&lhist[hofs + s1], hf[u]);
-            atomicAdd(&lhist[s2], gf[u]);
-            atomicAdd(&lhist[hofs + s2], hf[u]);
-            atomicAdd(&lhist[s3], gf[u]);
-            atomicAdd(&lhist[hofs + s3], hf[u]);
+            ru[u] = r + u * step;
+            keep[u] = FILTER == HIST_FILTER_OFF ||
+                      hist_row_kept((int)bins_c[ru[u] * nfeat + flt_feat], missing_bin, flt_bin,
+                                    flt_dl, flt_left);
           }
+          hist_add_rows_vec4<BinT, FILTER != HIST_FILTER_OFF>(lhist, hofs, bins_c, gh_c, ru, keep,
+                                                              nfeat, fg_start, nd, stride, scale_g,
+                                                              scale_h);
         }
       }
-    }
-    for (; r < node.end; r += step) {
-      const float2 gp = gh_c[r];
-      const unsigned long long gfix = (unsigned long long)(long long)llrintf(gp.x * scale_g);
-      const unsigned long long hfix = (unsigned long long)(long long)llrintf(gp.y * scale_h);
-      const BinT* rp = bins_c + (long long)r * nfeat + fg_start;
-      if (vec4) {
-        const uchar4* rp4 = reinterpret_cast<const uchar4*>(rp);
-        #pragma unroll 2
-        for (int f4 = 0; f4 < (nf_group >> 2); ++f4) {
-          const uchar4 b4 = rp4[f4];
-          const int base = (f4 << 2) * stride;
-          const int s0 = lds_pad_slot(base + (int)b4.x);
-          const int s1 = lds_pad_slot(base + stride + (int)b4.y);
-          const int s2 = lds_pad_slot(base + 2 * stride + (int)b4.z);
-          const int s3 = lds_pad_slot(base + 3 * stride + (int)b4.w);
-          atomicAdd(&lhist[s0], gfix);
-          atomicAdd(&lhist[hofs + s0], hfix);
-          atomicAdd(&lhist[s1], gfix);
-          atomicAdd(&lhist[hofs + s1], hfix);
-          atomicAdd(&lhist[s2], gfix);
-          atomicAdd(&lhist[hofs + s2], hfix);
-          atomicAdd(&lhist[s3], gfix);
-          atomicAdd(&lhist[hofs + s3], hfix);
-        }
-        continue;
-      }
-      #pragma unroll 4
-      for (int f = 0; f < nf_group; ++f) {
-        const int slot2 = lds_pad_slot(f * stride + (int)rp[f]);
-        atomicAdd(&lhist[slot2], gfix);
-        atomicAdd(&lhist[hofs + slot2], hfix);
+      for (; r < node.end; r += step) {
+        if (FILTER != HIST_FILTER_OFF &&
+            !hist_row_kept((int)bins_c[r * nfeat + flt_feat], missing_bin, flt_bin, flt_dl,
+                           flt_left))
+          continue;
+        hist_add_row<BinT>(lhist, hofs, bins_c, gh_c, r, vec4, nfeat, fg_start, nf_group, stride,
+                           scale_g, scale_h);
       }
     }
     __syncthreads();
@@ -976,7 +1139,7 @@ __global__ __launch_bounds__(HIST_BLOCK) void partition_device_kernel(
     const LevelNode* __restrict__ nodes, const int* __restrict__ part_prefix,
     const LevelWork* __restrict__ work, const float* __restrict__ split_packed,
     int* __restrict__ counters, int k, int nfeat, int missing_bin,
-    int copy_payload) {
+    int copy_payload, int copy_rows) {
   __shared__ int ldest[CPART_TILE];
   __shared__ int lcnt, rcnt, lbase, rbase;
   const int total = work->part_total;
@@ -1056,11 +1219,15 @@ __global__ __launch_bounds__(HIST_BLOCK) void partition_device_kernel(
               reinterpret_cast<const float*>(src_gh)[(tile + i) * 2 + half];
         }
       }
-      for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
-        const int d = ldest[i];
-        const long long dst =
-            d >= 0 ? (long long)node.start + lbase + d : (long long)node.end - 1 - rbase - (~d);
-        dst_rows[dst] = src_rows[tile + i];
+      // row ids feed the leaf scatter only: a tree whose margins are updated
+      // by traversal never reads them (copy_rows == 0)
+      if (copy_rows) {
+        for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
+          const int d = ldest[i];
+          const long long dst =
+              d >= 0 ? (long long)node.start + lbase + d : (long long)node.end - 1 - rbase - (~d);
+          dst_rows[dst] = src_rows[tile + i];
+        }
       }
       __syncthreads();
     }
@@ -1972,46 +2139,80 @@ void grow_make_root(torch::Tensor nodes, torch::Tensor hist_prefix, torch::Tenso
 void grow_make_level(torch::Tensor cur, torch::Tensor splits, torch::Tensor counts,
                      torch::Tensor node_gh, torch::Tensor nxt, torch::Tensor nxt_gh,
                      torch::Tensor hist_prefix, torch::Tensor part_prefix, torch::Tensor work,
-                     int64_t k, int64_t rows_per_block, int64_t max_blocks) {
+                     int64_t k, int64_t rows_per_block, int64_t max_blocks, int64_t filtered) {
   hipLaunchKernelGGL(make_level_kernel, dim3(1), dim3(GROW_MAX_SLOTS), 0, current_stream(),
                      (const LevelNode*)cur.data_ptr<int>(), splits.data_ptr<float>(),
                      counts.data_ptr<int>(), node_gh.data_ptr<float>(),
                      (LevelNode*)nxt.data_ptr<int>(), nxt_gh.data_ptr<float>(),
                      hist_prefix.data_ptr<int>(), part_prefix.data_ptr<int>(),
                      (LevelWork*)work.data_ptr<int>(), (int)k, (int)rows_per_block,
-                     (int)max_blocks);
+                     (int)max_blocks, (int)filtered);
 }
 
 // dispatch helper: BLOCK is a compile-time launch bound (256 grouped-slab,
-// 512 single full-feature slab)
+// 512 single full-feature slab); FILTER: see hist_device_kernel
+template <typename BinT, int FILTER>
+static void launch_hist_device_impl(int grid, int hist_block, size_t lds_bytes, hipStream_t stream,
+                               const BinT* bins_c, const float2* gh_c, const LevelNode* nodes,
+                               const int* hist_prefix, const LevelWork* work,
+                               unsigned long long* acc, int k, int nfeat, int stride,
+                               int n_groups, int feats_per_group, const float* gh_max,
+                               int rows_per_block, int slot_lo, int slot_hi,
+                               const float* par_splits, int missing_bin, int queue_ofs) {
+  // hipGraph kernel nodes validate dynamic LDS against the function's
+  // max-dynamic-shared attribute (plain launches do not): without this
+  // opt-in a captured full-slab launch (>64 KB) reads a truncated LDS
+  // allocation and memory-faults on replay (gfx950 allows 160 KB).
+  static bool lds_attr_set = [] {
+    (void)hipFuncSetAttribute((const void*)(hist_device_kernel<BinT, 512, FILTER>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)(hist_device_kernel<BinT, HIST_BLOCK, FILTER>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return true;
+  }();
+  (void)lds_attr_set;
+  if (hist_block == 512) {
+    hipLaunchKernelGGL((hist_device_kernel<BinT, 512, FILTER>), dim3(grid), dim3(512),
+                       lds_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work, acc, k, nfeat,
+                       stride, n_groups, feats_per_group, gh_max, rows_per_block, slot_lo,
+                       slot_hi, par_splits, missing_bin, queue_ofs);
+  } else {
+    hipLaunchKernelGGL((hist_device_kernel<BinT, HIST_BLOCK, FILTER>), dim3(grid),
+                       dim3(HIST_BLOCK), lds_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work,
+                       acc, k, nfeat, stride, n_groups, feats_per_group, gh_max, rows_per_block,
+                       slot_lo, slot_hi, par_splits, missing_bin, queue_ofs);
+  }
+}
+
 template <typename BinT>
 static void launch_hist_device(int grid, int hist_block, size_t lds_bytes, hipStream_t stream,
                                const BinT* bins_c, const float2* gh_c, const LevelNode* nodes,
                                const int* hist_prefix, const LevelWork* work,
                                unsigned long long* acc, int k, int nfeat, int stride,
                                int n_groups, int feats_per_group, const float* gh_max,
-                               int rows_per_block, int slot_lo = 0, int slot_hi = 1 << 30) {
-  // hipGraph kernel nodes validate dynamic LDS against the function's
-  // max-dynamic-shared attribute (plain launches do not): without this
-  // opt-in a captured full-slab launch (>64 KB) reads a truncated LDS
-  // allocation and memory-faults on replay (gfx950 allows 160 KB).
-  static bool lds_attr_set = [] {
-    (void)hipFuncSetAttribute((const void*)(hist_device_kernel<BinT, 512>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)(hist_device_kernel<BinT, HIST_BLOCK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();
-  (void)lds_attr_set;
-  if (hist_block == 512) {
-    hipLaunchKernelGGL((hist_device_kernel<BinT, 512>), dim3(grid), dim3(512), lds_bytes, stream,
-                       bins_c, gh_c, nodes, hist_prefix, work, acc, k, nfeat, stride, n_groups,
-                       feats_per_group, gh_max, rows_per_block, slot_lo, slot_hi);
+                               int rows_per_block, int slot_lo = 0, int slot_hi = 1 << 30,
+                               const float* par_splits = nullptr, int missing_bin = -1,
+                               bool predicate_only = false) {
+  // filter mode when parent split records are given. The per-wave row queues
+  // of the compacting form go behind the slab: taken for the single-slab
+  // block (one block per CU either way) when both fit, so they never cost
+  // occupancy; grouped slabs keep plain predication.
+  const size_t queue_bytes = (size_t)(hist_block / 64) * HIST_QUEUE_ROWS * sizeof(int);
+  if (par_splits == nullptr) {
+    launch_hist_device_impl<BinT, HIST_FILTER_OFF>(
+        grid, hist_block, lds_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work, acc, k,
+        nfeat, stride, n_groups, feats_per_group, gh_max, rows_per_block, slot_lo, slot_hi,
+        nullptr, missing_bin, 0);
+  } else if (!predicate_only && hist_block == 512 && lds_bytes + queue_bytes <= 158 * 1024) {
+    launch_hist_device_impl<BinT, HIST_FILTER_COMPACT>(
+        grid, hist_block, lds_bytes + queue_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work,
+        acc, k, nfeat, stride, n_groups, feats_per_group, gh_max, rows_per_block, slot_lo,
+        slot_hi, par_splits, missing_bin, (int)(lds_bytes / sizeof(unsigned long long)));
   } else {
-    hipLaunchKernelGGL((hist_device_kernel<BinT, HIST_BLOCK>), dim3(grid), dim3(HIST_BLOCK),
-                       lds_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work, acc, k, nfeat,
-                       stride, n_groups, feats_per_group, gh_max, rows_per_block, slot_lo,
-                       slot_hi);
+    launch_hist_device_impl<BinT, HIST_FILTER_PREDICATE>(
+        grid, hist_block, lds_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work, acc, k,
+        nfeat, stride, n_groups, feats_per_group, gh_max, rows_per_block, slot_lo, slot_hi,
+        par_splits, missing_bin, 0);
   }
 }
 
@@ -2020,9 +2221,20 @@ void grow_hist_level(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor nod
                      int64_t k, int64_t nfeat, int64_t stride, int64_t n_groups,
                      int64_t feats_per_group, torch::Tensor gh_max, int64_t rows_per_block,
                      int64_t grid, int64_t lds_words, int64_t hist_block,
-                     int64_t slot_lo, int64_t slot_hi) {
+                     int64_t slot_lo, int64_t slot_hi, torch::Tensor par_splits,
+                     int64_t missing_bin, int64_t predicate_only) {
   const size_t lds_bytes = (size_t)lds_words * sizeof(unsigned long long);
   auto stream = current_stream();
+  // filter mode (see hist_device_kernel): the parent level's [k/2, 6] split
+  // records; an empty tensor keeps the plain build
+  const float* par_ptr = nullptr;
+  if (par_splits.numel() > 0) {
+    CHECK_GPU(par_splits);
+    TORCH_CHECK(k >= 2 && par_splits.scalar_type() == torch::kFloat32 &&
+                    par_splits.is_contiguous() && par_splits.numel() >= (k >> 1) * 6,
+                "grow_hist_level: parent split records must be a contiguous float32 [k/2, 6]");
+    par_ptr = par_splits.data_ptr<float>();
+  }
   if (bins_c.scalar_type() == torch::kUInt8) {
     launch_hist_device<unsigned char>(
         (int)grid, (int)hist_block, lds_bytes, stream, bins_c.data_ptr<unsigned char>(),
@@ -2030,7 +2242,7 @@ void grow_hist_level(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor nod
         hist_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
         (unsigned long long*)acc.data_ptr<int64_t>(), (int)k, (int)nfeat, (int)stride,
         (int)n_groups, (int)feats_per_group, gh_max.data_ptr<float>(), (int)rows_per_block,
-        (int)slot_lo, (int)slot_hi);
+        (int)slot_lo, (int)slot_hi, par_ptr, (int)missing_bin, predicate_only != 0);
   } else {
     launch_hist_device<short>(
         (int)grid, (int)hist_block, lds_bytes, stream, bins_c.data_ptr<short>(),
@@ -2038,7 +2250,7 @@ void grow_hist_level(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor nod
         hist_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
         (unsigned long long*)acc.data_ptr<int64_t>(), (int)k, (int)nfeat, (int)stride,
         (int)n_groups, (int)feats_per_group, gh_max.data_ptr<float>(), (int)rows_per_block,
-        (int)slot_lo, (int)slot_hi);
+        (int)slot_lo, (int)slot_hi, par_ptr, (int)missing_bin, predicate_only != 0);
   }
 }
 
@@ -2079,9 +2291,11 @@ static bool launch_part_lds(int grid, hipStream_t stream, const unsigned char* s
                             unsigned char* dst_bins, float2* dst_gh, int* dst_rows,
                             const LevelNode* nodes, const int* part_prefix,
                             const LevelWork* work, const float* split_packed, int* counters,
-                            int k, int nfeat, int missing_bin, int copy_payload) {
+                            int k, int nfeat, int missing_bin, int copy_payload,
+                            int copy_rows) {
   const int tile = part_lds_mode();
-  if (tile == 0 || (nfeat & 3) != 0) return false;
+  // the staged variant always moves row ids: not selected without them
+  if (tile == 0 || (nfeat & 3) != 0 || !copy_rows) return false;
   const size_t lds = (size_t)tile * (8 + (size_t)(nfeat >> 2) * 4 + 8);
   if (lds > 158 * 1024) return false;
   if (tile == 2048) {
@@ -2103,7 +2317,7 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
                           torch::Tensor nodes, torch::Tensor part_prefix, torch::Tensor work,
                           torch::Tensor split_packed, torch::Tensor counters, int64_t k,
                           int64_t nfeat, int64_t missing_bin, int64_t grid,
-                          int64_t copy_payload) {
+                          int64_t copy_payload, int64_t copy_rows) {
   auto stream = current_stream();
   if (src_bins.scalar_type() == torch::kUInt8) {
     if (launch_part_lds((int)grid, stream, src_bins.data_ptr<unsigned char>(),
@@ -2112,7 +2326,7 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
                         dst_rows.data_ptr<int>(), (const LevelNode*)nodes.data_ptr<int>(),
                         part_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
                         split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)k,
-                        (int)nfeat, (int)missing_bin, (int)copy_payload))
+                        (int)nfeat, (int)missing_bin, (int)copy_payload, (int)copy_rows))
       return;
     hipLaunchKernelGGL(partition_device_kernel<unsigned char>, dim3((int)grid), dim3(HIST_BLOCK),
                        0, stream, src_bins.data_ptr<unsigned char>(),
@@ -2121,7 +2335,7 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
                        dst_rows.data_ptr<int>(), (const LevelNode*)nodes.data_ptr<int>(),
                        part_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
                        split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)k,
-                       (int)nfeat, (int)missing_bin, (int)copy_payload);
+                       (int)nfeat, (int)missing_bin, (int)copy_payload, (int)copy_rows);
   } else {
     hipLaunchKernelGGL(partition_device_kernel<short>, dim3((int)grid), dim3(HIST_BLOCK), 0,
                        stream, src_bins.data_ptr<short>(), (const float2*)src_gh.data_ptr<float>(),
@@ -2130,7 +2344,7 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
                        (const LevelNode*)nodes.data_ptr<int>(), part_prefix.data_ptr<int>(),
                        (const LevelWork*)work.data_ptr<int>(), split_packed.data_ptr<float>(),
                        counters.data_ptr<int>(), (int)k, (int)nfeat, (int)missing_bin,
-                       (int)copy_payload);
+                       (int)copy_payload, (int)copy_rows);
   }
 }
 
@@ -2173,9 +2387,16 @@ void grow_tree_enqueue(
     int64_t feats_per_group, int64_t lds_words, int64_t has_missing, int64_t missing_bin,
     int64_t rows_per_block, int64_t max_blocks, int64_t hist_grid, int64_t part_grid,
     double reg_lambda, double reg_alpha, double gamma_, double min_child_weight,
-    int64_t hist_block, int64_t skip_last_partition) {
+    int64_t hist_block, int64_t skip_last_partition, int64_t filter_deepest) {
   CHECK_GPU(init_bins);
   auto stream = current_stream();
+  // Margins updated by traversal (skip_last_partition): nothing reads row
+  // ids or the deepest level's ranges. With filter_deepest the partition of
+  // level D-2 goes too: level D-1's histograms stream the ranges level D-2
+  // read and keep each build child's rows by the parent's split
+  // (filter_deepest == 2: by plain predication even where compaction fits).
+  const bool filter_last = skip_last_partition && filter_deepest && D >= 2;
+  const int copy_rows = skip_last_partition ? 0 : 1;
   const long long slots2 = (long long)nfeat * stride * 2;
   const bool u8 = init_bins.scalar_type() == torch::kUInt8;
   const size_t lds_bytes = (size_t)lds_words * sizeof(unsigned long long);
@@ -2211,6 +2432,9 @@ void grow_tree_enqueue(
     int* hp_d = hp[d].data_ptr<int>();
     int* pp_d = pp[d].data_ptr<int>();
     LevelWork* work_d = (LevelWork*)(work.data_ptr<int>() + 2 * d);
+    const bool filtered = filter_last && d == (int)D - 1;
+    const float* par_splits =
+        filtered ? splits.data_ptr<float>() + (long long)((k >> 1) - 1) * 6 : nullptr;
 
     if (d == 0) {
       hipLaunchKernelGGL(make_root_kernel, dim3(1), dim3(1), 0, stream, nodes_d, hp_d, pp_d,
@@ -2223,11 +2447,14 @@ void grow_tree_enqueue(
                          splits.data_ptr<float>() + (long long)pbase * 6,
                          counts.data_ptr<int>() + (long long)pbase * 2,
                          node_gh.data_ptr<float>() + (long long)pbase * 2, nodes_d, gh_d, hp_d,
-                         pp_d, work_d, pk, (int)rows_per_block, (int)max_blocks);
+                         pp_d, work_d, pk, (int)rows_per_block, (int)max_blocks,
+                         filtered ? 1 : 0);
     }
 
-    const bool level0 = d == 0;
-    const bool par = (d % 2) == 1;
+    // a filtered level reads what the level above it read
+    const int sd = filtered ? d - 1 : d;
+    const bool level0 = sd == 0;
+    const bool par = (sd % 2) == 1;
     const void* src_bins = level0 ? init_bins.data_ptr() : (par ? bins1.data_ptr() : bins0.data_ptr());
     const float2* src_gh = (const float2*)(level0 ? init_gh.data_ptr<float>()
                                                   : (par ? gh1.data_ptr<float>() : gh0.data_ptr<float>()));
@@ -2244,13 +2471,14 @@ void grow_tree_enqueue(
           (int)hist_grid, (int)hist_block, lds_bytes, stream, (const unsigned char*)src_bins,
           src_gh, nodes_d, hp_d, work_d, (unsigned long long*)acc.data_ptr<int64_t>(), k,
           (int)nfeat, (int)stride, (int)n_groups, (int)feats_per_group,
-          gh_max.data_ptr<float>(), (int)rows_per_block);
+          gh_max.data_ptr<float>(), (int)rows_per_block, 0, 1 << 30, par_splits,
+          (int)missing_bin, filter_deepest == 2);
     } else {
       launch_hist_device<short>(
           (int)hist_grid, (int)hist_block, lds_bytes, stream, (const short*)src_bins, src_gh,
           nodes_d, hp_d, work_d, (unsigned long long*)acc.data_ptr<int64_t>(), k, (int)nfeat,
           (int)stride, (int)n_groups, (int)feats_per_group, gh_max.data_ptr<float>(),
-          (int)rows_per_block);
+          (int)rows_per_block, 0, 1 << 30, par_splits, (int)missing_bin, filter_deepest == 2);
     }
 
     {
@@ -2294,21 +2522,23 @@ void grow_tree_enqueue(
     // margins updated by traversal: nothing consumes the deepest level's
     // row ids and counts, so that level is not partitioned at all
     if (!copy_payload && skip_last_partition) continue;
+    // ... and with the filtered deepest histogram, neither is level D-2
+    if (filter_last && d == (int)D - 2) continue;
     if (u8) {
       if (!launch_part_lds((int)part_grid, stream, (const unsigned char*)src_bins, src_gh,
                            src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d, pp_d,
                            work_d, splits_d, counts_d, k, (int)nfeat, (int)missing_bin,
-                           copy_payload))
+                           copy_payload, copy_rows))
         hipLaunchKernelGGL(partition_device_kernel<unsigned char>, dim3((int)part_grid),
                            dim3(HIST_BLOCK), 0, stream, (const unsigned char*)src_bins, src_gh,
                            src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d, pp_d,
                            work_d, splits_d, counts_d, k, (int)nfeat, (int)missing_bin,
-                           copy_payload);
+                           copy_payload, copy_rows);
     } else {
       hipLaunchKernelGGL(partition_device_kernel<short>, dim3((int)part_grid), dim3(HIST_BLOCK),
                          0, stream, (const short*)src_bins, src_gh, src_rows, (short*)dst_bins,
                          dst_gh, dst_rows, nodes_d, pp_d, work_d, splits_d, counts_d, k,
-                         (int)nfeat, (int)missing_bin, copy_payload);
+                         (int)nfeat, (int)missing_bin, copy_payload, copy_rows);
     }
   }
 }

@@ -773,6 +773,18 @@ class _V1TreeState:
 
 _GROW_HIST_GRID = int(_os.environ.get("SMXGB_GROW_HIST_GRID", "1536"))
 _GROW_PART_GRID = int(_os.environ.get("SMXGB_GROW_PART_GRID", "4096"))
+# How a tree whose margins are updated by traversal builds its deepest
+# level's histograms: "filter" streams the ranges of the level above and
+# keeps each build child's rows by the parent's split (that level is then not
+# partitioned either); "partition" keeps the partition for A/B runs.
+# "filter-predicate" is "filter" held to plain predication where the kernel
+# would compact the kept rows per wave (A/B of the two forms).
+_DEEPEST_HIST = _os.environ.get("SMXGB_DEEPEST_HIST", "filter")
+_DEEPEST_HIST_MODES = {"partition": 0, "filter": 1, "filter-predicate": 2}
+if _DEEPEST_HIST not in _DEEPEST_HIST_MODES:
+    raise ValueError(
+        f"SMXGB_DEEPEST_HIST must be one of {sorted(_DEEPEST_HIST_MODES)}, got {_DEEPEST_HIST!r}"
+    )
 
 
 def interaction_union_bitsets(interaction_sets, f):
@@ -914,6 +926,7 @@ class DeviceGrower:
             self.rows_per_block, _MAX_BLOCKS_PER_JOB, _GROW_HIST_GRID, _GROW_PART_GRID,
             reg_lambda, reg_alpha, gamma, mcw, self.hist_block,
             1 if self.traverse else 0,
+            _DEEPEST_HIST_MODES[_DEEPEST_HIST],
         )
         if not hasattr(self, "_pinned"):
             self._pinned = (
@@ -963,7 +976,7 @@ class DeviceGrower:
             # captured body must be allocation-free — see _enqueue_body)
             if rootsum is None:
                 rootsum = st._gh_init.to(torch.float64).sum(0)
-            key = (st.cap, split_params, self.traverse)
+            key = (st.cap, split_params, self.traverse, _DEEPEST_HIST)
             dbg = _os.environ.get("SMXGB_GRAPH_DEBUG") == "1"
 
             def _d(msg):
@@ -1059,6 +1072,14 @@ class DeviceGrower:
         comm.allreduce_(root_gh)
         self.node_gh[0] = root_gh.to(torch.float32)
 
+        # traversal needs no row ids; with the filtered deepest histogram
+        # level D-2 is not partitioned either (see grow_tree_enqueue)
+        filter_mode = _DEEPEST_HIST_MODES[_DEEPEST_HIST]
+        filter_last = self.traverse and filter_mode != 0 and self.D >= 2
+        predicate_only = 1 if filter_mode == 2 else 0
+        copy_rows = 0 if self.traverse else 1
+        no_splits = torch.empty(0, dtype=torch.float32, device=self.splits.device)
+
         for d in range(self.D):
             k = 1 << d
             base = k - 1
@@ -1066,6 +1087,8 @@ class DeviceGrower:
             gh_d = self.node_gh[base : base + k]
             splits_d = self.splits[base : base + k]
             counts_d = self.counts[base : base + k]
+            filtered = filter_last and d == self.D - 1
+            par_splits = self.splits[(k >> 1) - 1 : k - 1] if filtered else no_splits
 
             if d == 0:
                 _K.grow_make_root(nodes_d, self.hp[0], self.pp[0], self.work[0],
@@ -1078,11 +1101,14 @@ class DeviceGrower:
                     self.counts[pbase : pbase + pk], self.node_gh[pbase : pbase + pk],
                     nodes_d, gh_d, self.hp[d], self.pp[d], self.work[d],
                     pk, self.rows_per_block, _MAX_BLOCKS_PER_JOB,
+                    1 if filtered else 0,
                 )
 
+            # a filtered level reads what the level above it read
+            sd = d - 1 if filtered else d
             src_bins, src_gh, src_rows = (
-                (st._bins_init, st._gh_init, st._rows_init) if d == 0
-                else (st._bins[d % 2], st._gh[d % 2], st._rows[d % 2])
+                (st._bins_init, st._gh_init, st._rows_init) if sd == 0
+                else (st._bins[sd % 2], st._gh[sd % 2], st._rows[sd % 2])
             )
             acc_d = self.acc[:k]
             acc_d.zero_()
@@ -1109,7 +1135,7 @@ class DeviceGrower:
                     src_bins, src_gh, nodes_d, self.hp[d], self.work[d], acc_d,
                     k, f, stride, self.n_groups, self.feats_per_group, scale,
                     self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
-                    0, mid,
+                    0, mid, par_splits, missing_bin, predicate_only,
                 )
                 c1 = acc_d[0:mid:2] + acc_d[1:mid:2]
                 w1 = comm.allreduce_async_(c1)
@@ -1117,7 +1143,7 @@ class DeviceGrower:
                     src_bins, src_gh, nodes_d, self.hp[d], self.work[d], acc_d,
                     k, f, stride, self.n_groups, self.feats_per_group, scale,
                     self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
-                    mid, k,
+                    mid, k, par_splits, missing_bin, predicate_only,
                 )
                 c2 = acc_d[mid::2] + acc_d[mid + 1 :: 2]
                 w2 = comm.allreduce_async_(c2)
@@ -1132,7 +1158,7 @@ class DeviceGrower:
                     src_bins, src_gh, nodes_d, self.hp[d], self.work[d], acc_d,
                     k, f, stride, self.n_groups, self.feats_per_group, scale,
                     self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
-                    0, 1 << 30,
+                    0, 1 << 30, par_splits, missing_bin, predicate_only,
                 )
                 if comm is not None:
                     if k == 1:
@@ -1167,12 +1193,15 @@ class DeviceGrower:
                 # margins updated by traversal: nothing reads the deepest
                 # level's row ids or counts
                 continue
+            if filter_last and d == self.D - 2:
+                continue
             dst = 1 - d % 2
             _K.grow_partition_level(
                 src_bins, src_gh, src_rows, st._bins[dst], st._gh[dst], st._rows[dst],
                 nodes_d, self.pp[d], self.work[d], splits_d, counts_d,
                 k, f, missing_bin, _GROW_PART_GRID,
                 1 if d < self.D - 1 else 0,  # last level feeds leaf_update only
+                copy_rows,
             )
         # (the grower decides _level0 from whether the root split)
 
