@@ -124,13 +124,16 @@ class HistGrower:
                 self._monotone_host = [int(c) for c in mono]
         # "device" or "per_level": which grower path the last tree took
         self.grow_path = None
-        # On a backend with a device grower the per-level depthwise loop
-        # reproduces that grower's arithmetic, so both paths grow the same
-        # trees: the root (G, H) rounded to float32 before leaf weights
-        # subtract from it (the device reads node_gh[0] back), and float32
-        # node sums into the split scan. Elsewhere it keeps float64 sums.
+        # On a backend that declares MIRRORS_DEVICE_GROWER (the HIP backends:
+        # dense, which has the device grower, and sparse, which grows per
+        # level only) the per-level depthwise loop reproduces the device
+        # grower's arithmetic, so every device path grows the same trees:
+        # the root (G, H) rounded to float32 before leaf weights subtract
+        # from it (the device reads node_gh[0] back), and float32 node sums
+        # into the split scan. Elsewhere it keeps float64 sums.
         self._mirror_device = (
-            hasattr(self.backend, "DeviceGrower") and self.p.grow_policy != "lossguide"
+            bool(getattr(self.backend, "MIRRORS_DEVICE_GROWER", False))
+            and self.p.grow_policy != "lossguide"
         )
         self._fallback_logged = False
         self.inter_sets = None

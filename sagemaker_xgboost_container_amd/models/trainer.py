@@ -42,13 +42,33 @@ _TRAIN_PARAM_KEYS = {
 }
 
 
+def sparse_auto_engage(n, f, nnz, free_bytes=None):
+    """The automatic (SMXGB_SPARSE unset) sparse-path decision.
+
+    On the host (`free_bytes` None): wide and at most half full. On a ROCm
+    device (`free_bytes` = free device memory) the same rule AND the dense
+    staging — float32 features plus uint8 bins, n*f*5 bytes — would take
+    more than half of the free memory. The device rule is memory-driven
+    only, so every job that fits keeps the dense device grower; where the
+    sparse path becomes faster than the dense one has not been measured
+    and is deliberately not encoded here.
+    """
+    if not (f >= 64 and nnz <= 0.5 * n * f):
+        return False
+    if free_bytes is None:
+        return True
+    return n * f * 5 > free_bytes / 2
+
+
 def _sparse_path_ok(dtrain, params, device, comm):
-    """Engage the CSR training backend (ops/sparse_ref.py)?
+    """Engage a CSR training backend (ops/sparse_ref.py on the host,
+    ops/hip_sparse.py on a ROCm device)?
 
     Wide sparse data (libsvm channels, reference data_utils.py:361) never
     densifies; small/narrow data keeps the dense fast path. Forced with
-    SMXGB_SPARSE=1 / disabled with SMXGB_SPARSE=0. The MI355X device path
-    densifies into HBM (288 GB), so this is the CPU-host path only.
+    SMXGB_SPARSE=1 / disabled with SMXGB_SPARSE=0. With a communicator the
+    GPU keeps the dense path (distributed device-sparse training is not
+    implemented).
     """
     import os as _os
 
@@ -57,7 +77,9 @@ def _sparse_path_ok(dtrain, params, device, comm):
         return False
     if not getattr(dtrain, "is_sparse", False):
         return False
-    if device.type != "cpu":
+    if device.type not in ("cpu", "cuda"):
+        return False
+    if device.type == "cuda" and comm is not None:
         return False
     if params.get("booster", "gbtree") != "gbtree":
         return False
@@ -67,7 +89,12 @@ def _sparse_path_ok(dtrain, params, device, comm):
         return True
     n, f = dtrain.num_row(), dtrain.num_col()
     nnz = dtrain.csr().nnz
-    return f >= 64 and nnz <= 0.5 * n * f
+    if device.type == "cpu":
+        return sparse_auto_engage(n, f, nnz)
+    if not sparse_auto_engage(n, f, nnz):
+        return False  # no device query for jobs the host rule already rejects
+    free_bytes, _total = torch.cuda.mem_get_info(device)
+    return sparse_auto_engage(n, f, nnz, free_bytes)
 
 
 def _resolve_device(params):
@@ -79,13 +106,28 @@ def _resolve_device(params):
     return torch.device("cpu")
 
 
+def _csr_tree_margin_fn(csr, device):
+    """tree -> (n,) margin contribution over the rows of a scipy CSR matrix
+    that stays sparse: the HIP traversal over an uploaded copy on a ROCm
+    device, the chunked host traversal on the CPU."""
+    if device.type == "cuda":
+        from ..ops import hip_sparse
+
+        dev_csr = hip_sparse.DeviceCSR(csr, device)
+        return lambda tree: hip_sparse.predict_tree_csr(tree, dev_csr)
+    from ..ops.sparse_ref import predict_tree_csr
+
+    return lambda tree: predict_tree_csr(tree, csr)
+
+
 class _EvalSet:
     """Resident eval data: dense features + incrementally updated margins.
 
     When the eval set IS the training DMatrix (the standard watchlist), it
     aliases the training tensors and margins — no copy, no per-round
     traversal (`is_train`). A wide sparse eval set stays CSR (`self.csr`)
-    and is traversed in bounded-memory chunks instead of densified.
+    and is traversed as CSR (on the device by the HIP CSR traversal, on the
+    host in bounded-memory chunks) instead of densified.
     """
 
     def __init__(self, dmatrix, name, device, n_outputs, base_margin_value,
@@ -104,6 +146,7 @@ class _EvalSet:
         if keep_sparse and getattr(dmatrix, "is_sparse", False):
             self.X = None
             self.csr = dmatrix.csr()
+            self._csr_margin = _csr_tree_margin_fn(self.csr, device)
         else:
             self.X = torch.as_tensor(dmatrix.to_dense(), dtype=torch.float32, device=device)
         self.y = torch.as_tensor(dmatrix.get_label(), dtype=torch.float32, device=device)
@@ -128,9 +171,7 @@ class _EvalSet:
     def tree_margin(self, backend, tree):
         """One tree's margin contribution over this eval set's rows."""
         if self.X is None:
-            from ..ops.sparse_ref import predict_tree_csr
-
-            return predict_tree_csr(tree, self.csr)
+            return self._csr_margin(tree)
         return backend.predict_tree(tree, self.X)
 
 
@@ -215,7 +256,8 @@ def train(
         Xcsr = dtrain.csr()
         X = None
         logger.info(
-            "Sparse training path engaged: %dx%d CSR, %d nnz (density %.4f) — no densification",
+            "Sparse training path engaged (backend %s): %dx%d CSR, %d nnz (density %.4f) — no densification",
+            "hip_sparse" if device.type == "cuda" else "sparse_ref",
             Xcsr.shape[0], Xcsr.shape[1], Xcsr.nnz, Xcsr.nnz / max(1, Xcsr.shape[0] * Xcsr.shape[1]),
         )
     else:
@@ -242,6 +284,10 @@ def train(
                 sample_weight=weight.cpu().numpy() if weight is not None else None,
                 comm=comm,
             )
+            if device.type != "cpu":
+                # cut finding and binning stay on the host; the CSR arrays
+                # (never an n x f matrix) move to the device
+                qm = qm.to(device)
         else:
             qm = quantize(X, max_bin=max_bin, sample_weight=weight, comm=comm)
     backend = backend_for(device)
@@ -254,11 +300,12 @@ def train(
     else:
         margin = torch.full((n, n_outputs), float(base_margin_value), dtype=torch.float32, device=device)
         # warm start: accumulate existing trees' contributions
+        train_csr_margin = (
+            _csr_tree_margin_fn(Xcsr, device) if sparse_mode and booster.trees else None
+        )
         for t_idx, tree in enumerate(booster.trees):
             if sparse_mode:
-                from ..ops.sparse_ref import predict_tree_csr
-
-                margin[:, booster.tree_info[t_idx]] += predict_tree_csr(tree, Xcsr)
+                margin[:, booster.tree_info[t_idx]] += train_csr_margin(tree)
             else:
                 margin[:, booster.tree_info[t_idx]] += backend.predict_tree(tree, X)
 

@@ -10,6 +10,9 @@ Two backends with one contract:
   must be present — a missing extension raises instead of silently falling
   back to eager PyTorch.
 
+Quantized CSR data has the same pair: ``sparse_ref`` on the host and
+``hip_sparse`` (csrc/smxgb_sparse.hip) on a ROCm device.
+
 Set ``SMXGB_FORCE_TORCH_OPS=1`` to force the reference backend on GPU
 (debugging/ablation only).
 """
@@ -31,10 +34,16 @@ def backend_for(device):
 
 
 def backend_for_qm(qm):
-    """Backend for a quantized matrix: the sparse backend for
-    SparseQuantizedMatrix, else the device backend."""
+    """Backend for a quantized matrix: a sparse backend for
+    SparseQuantizedMatrix (the HIP one when it lives on a ROCm device, the
+    host reference otherwise), else the device backend."""
     from . import sparse_ref
 
     if isinstance(qm, sparse_ref.SparseQuantizedMatrix):
+        if qm.device.type == "cuda":
+            # no eager fallback: a sparse matrix on the GPU needs the kernels
+            from . import hip_sparse
+
+            return hip_sparse
         return sparse_ref
     return backend_for(qm.device)

@@ -21,8 +21,7 @@
 
 #include <vector>
 
-#define WAVE 64
-#define HIST_BLOCK 256
+#include "smxgb_jobs.h"  // WAVE, HIST_BLOCK, CHECK_GPU, HistJob / PartJob / LeafJob
 
 // LDS histogram layout: separate g and h arrays (SoA). A 16-B interleaved
 // (g,h) slot can only start on 8 of the 32 bank groups (measured 75% of
@@ -37,40 +36,6 @@ __device__ __host__ inline long long lds_padded_words(long long pairs) {
 __device__ inline long long lds_half_words(long long pairs) {
   return pairs + (pairs >> 3) + 1;
 }
-#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be a ROCm device tensor")
-
-// ---------------------------------------------------------------------------
-// job descriptors (mirrored by host-side packing in ops/hip.py)
-// ---------------------------------------------------------------------------
-
-struct HistJob {
-  int start;        // row segment [start, end) in rowbuf
-  int end;
-  int hist_idx;     // output histogram index
-  int fg_start;     // feature group [fg_start, fg_end)
-  int fg_end;
-  int first_block;  // first grid block assigned to this job
-  int num_blocks;
-};
-
-struct PartJob {
-  int start;
-  int end;
-  int feature;
-  int split_bin;
-  int default_left;
-  int first_block;
-  int num_blocks;
-};
-
-struct LeafJob {
-  int start;
-  int end;
-  int parity;
-  float value;
-  int first_block;
-  int num_blocks;
-};
 
 // ---------------------------------------------------------------------------
 // histogram build
@@ -2578,9 +2543,11 @@ void find_splits(torch::Tensor hist, torch::Tensor parent, torch::Tensor nbins,
 }
 
 void init_text_parsers(pybind11::module_& m);
+void init_sparse_kernels(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_text_parsers(m);
+  init_sparse_kernels(m);
   m.def("hist_build", &hist_build, "batched LDS-staged fixed-point histogram build");
   m.def("hist_convert", &hist_convert, "fixed-point -> float32 histogram convert");
   m.def("partition", &partition, "batched two-ended row partition");

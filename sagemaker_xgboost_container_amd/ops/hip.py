@@ -15,6 +15,9 @@ import torch
 from . import torch_ref
 
 NAME = "hip"
+# models/grower.py: the per-level depthwise loop on this backend uses the
+# DeviceGrower's float32 root / node-sum arithmetic
+MIRRORS_DEVICE_GROWER = True
 
 try:
     from . import _smxgb_hip as _K  # built in-tree by setup.py build_ext --inplace

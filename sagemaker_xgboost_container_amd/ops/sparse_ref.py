@@ -16,9 +16,11 @@ This backend keeps the quantized matrix sparse:
 
 Implements the same backend interface as ops/torch_ref.py (make_tree_state,
 find_splits, compute_scale, hist_to_float) so models/grower.py runs
-unchanged. CPU-first: the MI355X path densifies into HBM (288 GB makes
-dense bins the faster layout on-device); this backend is for hosts and
-for data too wide even for HBM.
+unchanged. This is the HOST backend. Its device twin is ops/hip_sparse.py:
+`SparseQuantizedMatrix.to(device)` moves the quantized CSR arrays to a
+ROCm device, where HIP kernels build the same histograms and partition by
+binary search in the sorted column ids instead of the CSC scratch column.
+quantize_sparse (cut finding, binning) serves both and runs on the host.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -60,6 +62,63 @@ class SparseQuantizedMatrix:
     @property
     def missing_bin(self):
         return self.stride - 1
+
+    def _checked_sorted_csr(self):
+        """Host (indptr, indices, bin_data) with the invariants the kernels
+        index by: monotone offsets covering every entry, column ids in
+        [0, f) sorted within each row (sorted here when they are not), bin
+        ids below the missing slot."""
+        indptr = self.indptr.cpu().numpy().astype(np.int64, copy=False)
+        indices = self.indices.cpu().numpy()
+        bins = self.bin_data.cpu()
+        nnz = indices.shape[0]
+        if indptr.shape[0] != self.num_row + 1 or indptr[0] != 0 or indptr[-1] != nnz:
+            raise ValueError("indptr does not describe num_row rows over the stored entries")
+        counts = np.diff(indptr)
+        if nnz and (counts.min() < 0 or indices.min() < 0 or indices.max() >= self.num_col):
+            raise ValueError("CSR offsets or column ids out of range")
+        if nnz and int(bins.max()) >= self.stride - 1:
+            raise ValueError("bin id reaches the missing slot")
+        if nnz > 1:
+            # a descent inside a row (not across a row boundary) = unsorted
+            inner = np.ones(nnz - 1, dtype=bool)
+            starts = indptr[1:-1]
+            inner[starts[(starts > 0) & (starts < nnz)] - 1] = False
+            if bool((np.diff(indices.astype(np.int64)) < 0)[inner].any()):
+                row_of = np.repeat(np.arange(self.num_row, dtype=np.int64), counts)
+                order = np.lexsort((indices, row_of))
+                indices = indices[order]
+                bins = bins[torch.from_numpy(order)]
+        return indptr, indices, bins
+
+    def to(self, device):
+        """The matrix on `device` with per-row sorted column ids.
+
+        A ROCm device gets the CSR arrays only (int64 offsets, int32 column
+        ids, bins) plus cuts / nbins / cut_ptr: the device kernels find a
+        row's split feature by binary search and need no CSC mirror, which
+        therefore stays on the host. On the CPU the CSC mirror is kept."""
+        device = torch.device(device)
+        indptr, indices, bins = self._checked_sorted_csr()
+        on_cpu = device.type == "cpu"
+        idx_dtype = np.int64 if on_cpu else np.int32
+        csc = (None, None, None)
+        if on_cpu and self.csc_ptr is not None:
+            csc = (self.csc_ptr.cpu(), self.csc_rows.cpu(), self.csc_bins.cpu())
+        return SparseQuantizedMatrix(
+            csr_bins=(
+                torch.from_numpy(indptr).to(device),
+                torch.from_numpy(np.ascontiguousarray(indices, dtype=idx_dtype)).to(device),
+                bins.contiguous().to(device),
+            ),
+            csc=csc,
+            cuts=self.cuts.to(device),
+            cut_ptr=self.cut_ptr.to(device),
+            nbins=self.nbins.to(device),
+            stride=self.stride,
+            num_row=self.num_row,
+            num_col=self.num_col,
+        )
 
 
 def _merged_cuts_distributed(csc, f, max_bin, w, comm, n_candidates=None):

@@ -24,6 +24,7 @@ setup(
             name="sagemaker_xgboost_container_amd.ops._smxgb_hip",
             sources=[
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_kernels.hip",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_sparse.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/text_parsers.cpp",
             ],
             extra_compile_args={
