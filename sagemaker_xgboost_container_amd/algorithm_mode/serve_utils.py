@@ -8,7 +8,9 @@ csv/json/jsonlines/recordio-protobuf.
 
 The hot predict path runs this framework's batched HIP tree-traversal
 kernel when a GPU is present (Booster.predict -> ops.hip.predict_forest);
-on CPU hosts it uses the vectorized torch traversal.
+on CPU hosts it uses the vectorized torch traversal. A libsvm payload stays
+CSR from the parser to the booster (padding and trimming change the CSR
+shape), so Booster.predict's sparse route can serve it without an n x f image.
 """
 import json
 import os
@@ -216,7 +218,17 @@ def predict(model, model_format, dtest, input_content_type, objective=None):
         else:
             raise ValueError(f"Content type {content_type} is not supported")
 
-        if y < x:
+        if getattr(dtest, "is_sparse", False) and y != x:
+            # a CSR payload stays CSR: absent entries are missing, so widening
+            # the shape pads trailing features exactly as NaN columns would,
+            # and the extra column is dropped by a sparse column slice
+            csr = dtest.csr()
+            if y < x:
+                csr = csr_matrix((csr.data, csr.indices, csr.indptr), shape=(csr.shape[0], x))
+            else:
+                csr = csr[:, :x]
+            dtest = DMatrix(csr)
+        elif y < x:
             # libsvm payloads may omit trailing features: pad as missing
             dense = np.full((dtest.num_row(), x), np.nan, dtype=np.float32)
             dense[:, :y] = dtest.to_dense()

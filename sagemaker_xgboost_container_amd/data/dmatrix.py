@@ -207,6 +207,17 @@ def _load_uri(uri):
     raise exc.UserError(f"Unknown DMatrix format: {fmt}")
 
 
+def densify_csr_rows(csr, start, end):
+    """Dense float32 rows [start, end) of a CSR matrix. Entries ABSENT from
+    the matrix are missing (NaN), matching xgboost's sparse semantics;
+    explicit stored zeros stay 0."""
+    e0, e1 = int(csr.indptr[start]), int(csr.indptr[end])
+    dense = np.full((end - start, csr.shape[1]), np.nan, dtype=np.float32)
+    rows = np.repeat(np.arange(end - start), np.diff(csr.indptr[start:end + 1]))
+    dense[rows, csr.indices[e0:e1]] = csr.data[e0:e1]
+    return dense
+
+
 class DMatrix:
     """Feature matrix + per-row metadata (label, weight, base margin)."""
 
@@ -354,12 +365,7 @@ class DMatrix:
         """
         if self._dense is not None:
             return self._dense
-        csr = self._csr
-        n, f = csr.shape
-        dense = np.full((n, f), np.nan, dtype=np.float32)
-        rows = np.repeat(np.arange(n), np.diff(csr.indptr))
-        dense[rows, csr.indices] = csr.data
-        return dense
+        return densify_csr_rows(self._csr, 0, self._csr.shape[0])
 
     def csr(self):
         if self._csr is not None:

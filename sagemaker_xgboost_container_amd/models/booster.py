@@ -21,6 +21,13 @@ from .tree import Tree
 
 MODEL_VERSION = [3, 0, 5]  # schema-compatible xgboost version
 
+# predict() keeps a sparse DMatrix sparse once its dense float32 image would
+# exceed this many bytes: the per-launch staging budget the device explainers
+# already use (ops/hip.py SHAP_PARTIAL_CAP). The host route densifies at most
+# this much at a time.
+SPARSE_PREDICT_DENSE_BUDGET = 256 << 20
+
+
 
 def objective_params_from_json(obj_json, params):
     """Restore hyperparameters from a model/config objective block into
@@ -135,22 +142,26 @@ class Booster:
         self._predict_cache = None
 
     # -- prediction ----------------------------------------------------------
+    def _start_margin(self, n, device, base_margin):
+        """(n, k) float32 starting margin: the per-row base_margin when
+        given, else the objective's transform of base_score."""
+        k = self.n_outputs
+        if base_margin is not None:
+            return torch.as_tensor(
+                base_margin, dtype=torch.float32, device=device
+            ).reshape(n, k).clone()
+        base = self.objective().base_margin(self.base_score)
+        return torch.full((n, k), float(base), dtype=torch.float32, device=device)
+
     def _margin(self, X, iteration_range=None, base_margin=None):
         """Raw margin (n,) or (n, k) for dense float32 tensor X.
 
         `base_margin` (per-row, from the DMatrix) replaces the global
         base_score as the starting margin — xgboost semantics."""
-        obj = self.objective()
         n = X.shape[0]
         k = self.n_outputs
         device = X.device
-        if base_margin is not None:
-            margin = torch.as_tensor(
-                base_margin, dtype=torch.float32, device=device
-            ).reshape(n, k).clone()
-        else:
-            base = obj.base_margin(self.base_score)
-            margin = torch.full((n, k), float(base), dtype=torch.float32, device=device)
+        margin = self._start_margin(n, device, base_margin)
         lo, hi = 0, self.num_boosted_rounds()
         if iteration_range is not None and iteration_range != (0, 0):
             lo, hi = iteration_range
@@ -194,10 +205,14 @@ class Booster:
             raise ValueError(
                 "only one of pred_contribs, pred_interactions and pred_leaf may be requested"
             )
-        X = self._as_tensor(data, validate_features)
-        base_margin = getattr(data, "get_base_margin", lambda: None)()
         if ntree_limit:  # legacy alias: trees -> iterations
             iteration_range = (0, int(ntree_limit) // max(1, self._trees_per_round()))
+        if self._sparse_predict_route(data, explain=pred_contribs or pred_interactions):
+            if validate_features:
+                self._validate_features(data)
+            return self._predict_sparse(data, output_margin, iteration_range, pred_leaf)
+        X = self._as_tensor(data, validate_features)
+        base_margin = getattr(data, "get_base_margin", lambda: None)()
         if pred_contribs:
             return self._pred_contribs(
                 X, approx=approx_contribs, iteration_range=iteration_range,
@@ -220,24 +235,120 @@ class Booster:
             return self.n_outputs
         return self.iteration_indptr[1] - self.iteration_indptr[0]
 
+    def _validate_features(self, data):
+        """Feature count and names of a DMatrix against the model's (needs
+        num_col() and the names only, never the values)."""
+        if self.num_features and data.num_col() != self.num_features:
+            raise ValueError(
+                f"feature_names mismatch: model expects {self.num_features} features, "
+                f"got {data.num_col()}"
+            )
+        if (
+            self.feature_names
+            and data.feature_names
+            and list(data.feature_names) != list(self.feature_names)
+        ):
+            raise ValueError(
+                f"feature_names mismatch: {self.feature_names} vs {data.feature_names}"
+            )
+
+    def _predict_device(self):
+        """Where predict() runs: the GPU whenever there is one, unless
+        predictor=cpu_predictor forces host traversal."""
+        use_gpu = torch.cuda.is_available() and self.params.get("predictor") != "cpu_predictor"
+        return torch.device("cuda" if use_gpu else "cpu")
+
+    def _sparse_predict_route(self, data, explain=False):
+        """Does predict() keep this input sparse?
+
+        Yes for a sparse DMatrix holding a canonical CSR (sorted, no
+        duplicate column ids in a row; anything else keeps the densifying
+        path, whose last-duplicate-wins rule a search cannot reproduce) on a
+        tree booster, unless TreeSHAP output is asked for (n x (f + 1) dense
+        anyway). SMXGB_SPARSE_PREDICT=1 forces the route, =0 disables it;
+        unset, the rule is memory-driven like training's device rule: wide
+        and at most half full (trainer.sparse_auto_engage) AND a dense
+        float32 image beyond SPARSE_PREDICT_DENSE_BUDGET. Small payloads
+        therefore keep the dense kernel; where the CSR kernel becomes faster
+        than densify + dense is not encoded (profiles/r08_sparse_predict.md).
+        """
+        from ..data.dmatrix import DMatrix
+
+        flag = os.environ.get("SMXGB_SPARSE_PREDICT")
+        if flag == "0" or explain:
+            return False
+        if not isinstance(data, DMatrix) or not data.is_sparse:
+            return False
+        if self.booster_type not in ("gbtree", "dart"):
+            return False
+        csr = data.csr()
+        if flag != "1":
+            from .trainer import sparse_auto_engage
+
+            n, f = csr.shape
+            if not sparse_auto_engage(n, f, csr.nnz):
+                return False
+            if n * f * 4 <= SPARSE_PREDICT_DENSE_BUDGET:
+                return False
+        return bool(csr.has_canonical_format)
+
+    def _predict_sparse(self, data, output_margin, iteration_range, pred_leaf):
+        """predict() for a sparse DMatrix without its n x f image.
+
+        On a ROCm device the CSR arrays are uploaded as they are and the
+        forest runs over them (ops/hip_sparse.py predict_forest_csr /
+        pred_leaf_csr), equal bit for bit to the dense kernels on the
+        NaN-densified rows. Elsewhere rows are densified a budget-bounded
+        chunk at a time through the dense path and the chunks concatenated;
+        rows are independent, so that equals the full-densify result."""
+        from ..data.dmatrix import densify_csr_rows
+
+        csr = data.csr()
+        n, f = csr.shape
+        k = self.n_outputs
+        device = self._predict_device()
+        base_margin = data.get_base_margin()
+        if base_margin is not None:
+            base_margin = np.asarray(base_margin, dtype=np.float32).reshape(n, k)
+        t_begin, t_end = self._tree_range(iteration_range)
+
+        if device.type == "cuda" and ops.backend_for(device).NAME == "hip":
+            from ..ops import hip_sparse
+
+            dcsr = hip_sparse.DeviceCSR(csr, device)
+            flat = self._device_flat_forest(device, with_paths=False) if self.trees else None
+            if pred_leaf:
+                if flat is None:
+                    return np.zeros((n, 0), dtype=np.int32)
+                return hip_sparse.pred_leaf_csr(flat, dcsr, t_begin, t_end).cpu().numpy()
+            margin = self._start_margin(n, device, base_margin)
+            if flat is not None:
+                margin += hip_sparse.predict_forest_csr(flat, dcsr, k, t_begin, t_end)
+            margin = margin.squeeze(1) if k == 1 else margin
+        else:
+            step = max(1, SPARSE_PREDICT_DENSE_BUDGET // max(1, f * 4))
+            parts = []
+            for a in range(0, max(n, 1), step):  # an empty matrix is one empty chunk
+                b = min(n, a + step)
+                X = torch.as_tensor(densify_csr_rows(csr, a, b), dtype=torch.float32, device=device)
+                if pred_leaf:
+                    parts.append(self._pred_leaf(X, iteration_range=iteration_range))
+                else:
+                    bm = base_margin[a:b] if base_margin is not None else None
+                    parts.append(self._margin(X, iteration_range, base_margin=bm))
+            if pred_leaf:
+                return np.concatenate(parts, axis=0)
+            margin = torch.cat(parts, dim=0)
+        if output_margin:
+            return margin.cpu().numpy()
+        return self.objective().transform(margin).cpu().numpy()
+
     def _as_tensor(self, data, validate_features=True):
         from ..data.dmatrix import DMatrix
 
         if isinstance(data, DMatrix):
-            if validate_features and self.num_features and data.num_col() != self.num_features:
-                raise ValueError(
-                    f"feature_names mismatch: model expects {self.num_features} features, "
-                    f"got {data.num_col()}"
-                )
-            if (
-                validate_features
-                and self.feature_names
-                and data.feature_names
-                and list(data.feature_names) != list(self.feature_names)
-            ):
-                raise ValueError(
-                    f"feature_names mismatch: {self.feature_names} vs {data.feature_names}"
-                )
+            if validate_features:
+                self._validate_features(data)
             arr = data.to_dense()
         else:
             arr = np.asarray(data, dtype=np.float32)
@@ -252,9 +363,7 @@ class Booster:
         # size (100x500 trees: 0.085 ms GPU vs 0.70 ms CPU —
         # benchmarks/bench_predict_cpu_gpu.py), so GPU is always preferred;
         # predictor=cpu_predictor still forces host traversal
-        predictor = self.params.get("predictor")
-        use_gpu = torch.cuda.is_available() and predictor != "cpu_predictor"
-        return torch.as_tensor(arr, dtype=torch.float32, device="cuda" if use_gpu else "cpu")
+        return torch.as_tensor(arr, dtype=torch.float32, device=self._predict_device())
 
     def _cpu_flat_forest(self):
         """Flat forest on host for the contrib/leaf paths (cached)."""

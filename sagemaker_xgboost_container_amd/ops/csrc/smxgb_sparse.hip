@@ -270,6 +270,139 @@ __global__ __launch_bounds__(HIST_BLOCK) void predict_tree_csr_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// whole forest over raw CSR rows (Booster.predict on sparse data)
+// ---------------------------------------------------------------------------
+
+// most entries of one row group the launcher lets a block stage in LDS:
+// 8192 x (int, float) = 64 KiB of dynamic LDS
+#define PCSR_MAX_TILE 8192
+
+// csr_find over an LDS slice (int offsets into the tile)
+__device__ inline int tile_find(const int* cols, int lo, int hi, int feature) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    const int c = cols[mid];
+    if (c < feature) {
+      lo = mid + 1;
+    } else if (c > feature) {
+      hi = mid;
+    } else {
+      return mid;
+    }
+  }
+  return -1;
+}
+
+// The CSR twin of predict_kernel (LEAF = false) and pred_leaf_kernel
+// (LEAF = true), same work decomposition so the results are equal bit for
+// bit on the NaN-densified rows: an item is (row, c) with c < n_inner, where
+// c is a tree chunk (trees [t_begin + c * trees_per_chunk, ...) visited in
+// ascending order, each adding into out[c, row, tree_cls[t]]) or, for LEAF,
+// one tree (trees_per_chunk == 1, out[row, c] = tree-local leaf id).
+//
+// A block owns R consecutive rows and all n_inner items of each; blocks
+// grid-stride over such groups. The group's entries are contiguous in the
+// matrix: when they fit the tile (`tile` entries of dynamic LDS, column ids
+// then values) they are copied to LDS once (coalesced) and
+// every split node's binary search runs there; a longer group (one very
+// long row, say) searches global memory as predict_tree_csr_kernel does.
+// The choice is uniform over the block. The split rule is
+// predict_tree_csr_kernel's.
+template <bool LEAF>
+__device__ __forceinline__ void forest_csr_body(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ data, long long n, int rows_per_group,
+    const int* __restrict__ left, const int* __restrict__ right,
+    const int* __restrict__ feat, const float* __restrict__ thresh,
+    const unsigned char* __restrict__ defl, const float* __restrict__ value,
+    const int* __restrict__ tree_root, const int* __restrict__ tree_cls, int t_begin,
+    int t_end, void* __restrict__ out_raw, int k, int n_inner, int trees_per_chunk,
+    int tile) {
+  extern __shared__ int s_tile[];
+  int* s_col = s_tile;
+  float* s_val = (float*)(s_tile + tile);
+
+  const long long n_groups = (n + rows_per_group - 1) / rows_per_group;
+  for (long long g = blockIdx.x; g < n_groups; g += gridDim.x) {
+    const long long r0 = g * rows_per_group;
+    const int rows = (int)min((long long)rows_per_group, n - r0);
+    const long long e0 = indptr[r0];
+    const long long e1 = indptr[r0 + rows];
+    const bool staged = e1 - e0 <= tile;
+    __syncthreads();  // the previous group's searches are done with the tile
+    if (staged) {
+      const int cnt = (int)(e1 - e0);
+      for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+        s_col[i] = indices[e0 + i];
+        s_val[i] = data[e0 + i];
+      }
+    }
+    __syncthreads();
+
+    const long long items = (long long)rows * n_inner;
+    for (long long it = threadIdx.x; it < items; it += blockDim.x) {
+      const int lr = (int)(it / n_inner);
+      const int c = (int)(it - (long long)lr * n_inner);
+      const long long row = r0 + lr;
+      const long long lo = indptr[row];
+      const long long hi = indptr[row + 1];
+      const int tlo = (int)(lo - e0);  // used when staged only
+      const int thi = (int)(hi - e0);
+      const int ts = t_begin + c * trees_per_chunk;
+      const int te = min(t_end, ts + trees_per_chunk);
+      for (int t = ts; t < te; ++t) {
+        const int root = tree_root[t];
+        int nid = root;
+        int l;
+        while ((l = left[nid]) >= 0) {
+          const int f = feat[nid];
+          bool goleft = defl[nid] != 0;
+          if (staged) {
+            const int pos = tile_find(s_col, tlo, thi, f);
+            if (pos >= 0) {
+              const float fv = s_val[pos];
+              if (!isnan(fv)) goleft = fv < thresh[nid];
+            }
+          } else {
+            const long long pos = csr_find(indices, lo, hi, f);
+            if (pos >= 0) {
+              const float fv = data[pos];
+              if (!isnan(fv)) goleft = fv < thresh[nid];
+            }
+          }
+          nid = goleft ? l : right[nid];
+        }
+        if (LEAF) {
+          ((int*)out_raw)[row * n_inner + c] = nid - root;
+        } else {
+          ((float*)out_raw)[((long long)c * n + row) * k + tree_cls[t]] += value[nid];
+        }
+      }
+    }
+  }
+}
+
+#define FOREST_CSR_PARAMS                                                                 \
+  const long long *__restrict__ indptr, const int *__restrict__ indices,                  \
+      const float *__restrict__ data, long long n, int rows_per_group,                    \
+      const int *__restrict__ left, const int *__restrict__ right,                        \
+      const int *__restrict__ feat, const float *__restrict__ thresh,                     \
+      const unsigned char *__restrict__ defl, const float *__restrict__ value,            \
+      const int *__restrict__ tree_root, const int *__restrict__ tree_cls, int t_begin,   \
+      int t_end, void *__restrict__ out, int k, int n_inner, int trees_per_chunk, int tile
+#define FOREST_CSR_ARGS                                                                    \
+  indptr, indices, data, n, rows_per_group, left, right, feat, thresh, defl, value,        \
+      tree_root, tree_cls, t_begin, t_end, out, k, n_inner, trees_per_chunk, tile
+
+__global__ __launch_bounds__(HIST_BLOCK) void predict_forest_csr_kernel(FOREST_CSR_PARAMS) {
+  forest_csr_body<false>(FOREST_CSR_ARGS);
+}
+
+__global__ __launch_bounds__(HIST_BLOCK) void pred_leaf_csr_kernel(FOREST_CSR_PARAMS) {
+  forest_csr_body<true>(FOREST_CSR_ARGS);
+}
+
+// ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
 
@@ -397,7 +530,91 @@ void predict_tree_csr(torch::Tensor indptr, torch::Tensor indices, torch::Tensor
                      out.data_ptr<float>());
 }
 
+// Shared validation and launch of the forest-over-CSR kernel. `n_inner` is
+// the chunk count (margins, out = (n_inner, n, k) float32) or the tree count
+// (leaves, out = (n, n_inner) int32). Everything is checked on the host
+// before the launch; the offsets and column ids themselves are checked when
+// the matrix is uploaded (hip_sparse.DeviceCSR).
+template <bool LEAF>
+static void launch_forest_csr(torch::Tensor indptr, torch::Tensor indices, torch::Tensor data,
+                              torch::Tensor left, torch::Tensor right, torch::Tensor feat,
+                              torch::Tensor thresh, torch::Tensor defl, torch::Tensor value,
+                              torch::Tensor tree_root, torch::Tensor tree_cls, int64_t t_begin,
+                              int64_t t_end, torch::Tensor out, int64_t k, int64_t n_inner,
+                              int64_t trees_per_chunk, int64_t rows_per_group, int64_t tile) {
+  check_csr(indptr, indices);
+  CHECK_DEV(data, torch::kFloat32);
+  CHECK_DEV(left, torch::kInt32);
+  CHECK_DEV(right, torch::kInt32);
+  CHECK_DEV(feat, torch::kInt32);
+  CHECK_DEV(thresh, torch::kFloat32);
+  CHECK_DEV(defl, torch::kUInt8);
+  CHECK_DEV(value, torch::kFloat32);
+  CHECK_DEV(tree_root, torch::kInt32);
+  CHECK_DEV(tree_cls, torch::kInt32);
+  const auto out_dtype = LEAF ? torch::kInt32 : torch::kFloat32;
+  CHECK_DEV(out, out_dtype);
+  const long long n = indptr.size(0) - 1;
+  const long long nodes = left.numel();
+  TORCH_CHECK_VALUE(data.numel() == indices.numel(), "data and indices differ in size");
+  TORCH_CHECK_VALUE(right.numel() == nodes && feat.numel() == nodes && thresh.numel() == nodes &&
+                        defl.numel() == nodes && value.numel() == nodes,
+                    "forest node arrays differ in size");
+  TORCH_CHECK_VALUE(tree_cls.numel() == tree_root.numel(), "tree_root and tree_cls differ in size");
+  TORCH_CHECK_VALUE(0 <= t_begin && t_begin <= t_end && t_end <= tree_root.numel(),
+                    "tree range out of bounds");
+  TORCH_CHECK_VALUE(k >= 1 && n_inner >= 1 && trees_per_chunk >= 1 &&
+                        n_inner * trees_per_chunk >= t_end - t_begin &&
+                        n_inner * trees_per_chunk <= (1ll << 30) && t_end <= (1ll << 30),
+                    "tree chunking does not cover the tree range");
+  TORCH_CHECK_VALUE(rows_per_group >= 1 && rows_per_group <= (1 << 20),
+                    "rows_per_group out of range");
+  TORCH_CHECK_VALUE(tile >= 0 && tile <= PCSR_MAX_TILE, "LDS tile of ", tile,
+                    " entries exceeds ", PCSR_MAX_TILE);
+  TORCH_CHECK_VALUE(out.numel() == (LEAF ? n * n_inner : n_inner * n * k),
+                    LEAF ? "out must be (n, T) for n + 1 offsets"
+                         : "out must be (n_chunks, n, k) for n + 1 offsets");
+  if (n == 0 || t_end == t_begin) return;
+  const long long n_groups = (n + rows_per_group - 1) / rows_per_group;
+  const int grid = (int)std::min<long long>(n_groups, 4096);
+  const size_t lds = (size_t)tile * (sizeof(int) + sizeof(float));
+  hipLaunchKernelGGL(LEAF ? pred_leaf_csr_kernel : predict_forest_csr_kernel, dim3(grid), dim3(HIST_BLOCK), lds,
+                     sparse_stream(), (const long long*)indptr.data_ptr<int64_t>(),
+                     indices.data_ptr<int>(), data.data_ptr<float>(), n, (int)rows_per_group,
+                     left.data_ptr<int>(), right.data_ptr<int>(), feat.data_ptr<int>(),
+                     thresh.data_ptr<float>(), defl.data_ptr<unsigned char>(),
+                     value.data_ptr<float>(), tree_root.data_ptr<int>(),
+                     tree_cls.data_ptr<int>(), (int)t_begin, (int)t_end, out.data_ptr(), (int)k,
+                     (int)n_inner, (int)trees_per_chunk, (int)tile);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "forest-over-CSR kernel launch failed: ", hipGetErrorString(err));
+}
+
+void predict_forest_csr(torch::Tensor indptr, torch::Tensor indices, torch::Tensor data,
+                        torch::Tensor left, torch::Tensor right, torch::Tensor feat,
+                        torch::Tensor thresh, torch::Tensor defl, torch::Tensor value,
+                        torch::Tensor tree_root, torch::Tensor tree_cls, int64_t t_begin,
+                        int64_t t_end, torch::Tensor out, int64_t k, int64_t n_chunks,
+                        int64_t trees_per_chunk, int64_t rows_per_group, int64_t tile) {
+  launch_forest_csr<false>(indptr, indices, data, left, right, feat, thresh, defl, value,
+                           tree_root, tree_cls, t_begin, t_end, out, k, n_chunks,
+                           trees_per_chunk, rows_per_group, tile);
+}
+
+void pred_leaf_csr(torch::Tensor indptr, torch::Tensor indices, torch::Tensor data,
+                   torch::Tensor left, torch::Tensor right, torch::Tensor feat,
+                   torch::Tensor thresh, torch::Tensor defl, torch::Tensor value,
+                   torch::Tensor tree_root, torch::Tensor tree_cls, int64_t t_begin,
+                   int64_t t_end, torch::Tensor out, int64_t rows_per_group, int64_t tile) {
+  launch_forest_csr<true>(indptr, indices, data, left, right, feat, thresh, defl, value,
+                          tree_root, tree_cls, t_begin, t_end, out, 1, t_end - t_begin, 1,
+                          rows_per_group, tile);
+}
+
 void init_sparse_kernels(pybind11::module_& m) {
+  m.def("predict_forest_csr", &predict_forest_csr,
+        "summed margins of a flat forest over raw CSR rows, per tree chunk");
+  m.def("pred_leaf_csr", &pred_leaf_csr, "leaf index per (row, tree) over raw CSR rows");
   m.def("hist_sparse", &hist_sparse, "fixed-point histogram of stored CSR entries + job totals");
   m.def("hist_sparse_close", &hist_sparse_close, "missing slot = job total - present bins");
   m.def("partition_sparse", &partition_sparse, "batched two-ended row partition over CSR rows");

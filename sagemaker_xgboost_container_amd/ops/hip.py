@@ -383,6 +383,8 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
             [int(t.feature[t.left >= 0].max()) if (t.left >= 0).any() else -1 for t in trees],
             dtype=np.int64,
         ),
+        # largest class id: the CSR forest launcher checks it against k
+        "tree_cls_max": int(max(tree_info, default=0)),
         "n_trees": len(trees),
     }
 

@@ -1,4 +1,4 @@
-"""CDNA4 HIP backend for quantized CSR data (MI355X sparse training path).
+"""CDNA4 HIP backend for CSR data (MI355X sparse training and prediction).
 
 The device twin of ops/sparse_ref.py: a SparseQuantizedMatrix that lives on
 the GPU (`SparseQuantizedMatrix.to(device)`) trains without ever becoming an
@@ -19,6 +19,15 @@ loops unchanged. Kernels: csrc/smxgb_sparse.hip.
   by the grower.
 * margins of eval sets and warm-start replay: `predict_tree_csr` over the
   raw CSR values, equal to hip.predict_tree on the NaN-densified rows.
+* Booster.predict on a sparse DMatrix: `predict_forest_csr` (margins) and
+  `pred_leaf_csr` (leaf ids) run a whole hip.make_flat_forest dict over a
+  DeviceCSR in one launch. A block owns R consecutive rows and every tree
+  chunk (or tree) of them, stages the rows' entries in LDS when they fit
+  PREDICT_CSR_TILE and binary-searches there at every split node; longer
+  groups search global memory. The (row, tree-chunk) items, the tree order
+  inside a chunk and the fixed-order chunk reduce are the dense kernel's, so
+  the results equal hip.predict_forest_flat / hip.pred_leaf on the
+  NaN-densified rows bit for bit. TreeSHAP over CSR is not implemented.
 
 There is no DeviceGrower for this layout: HistGrower.grow_path stays
 "per_level", which mirrors the device grower's float32 node arithmetic
@@ -189,5 +198,102 @@ def predict_tree_csr(tree, csr, device=None):
     _K.predict_tree_csr(
         csr.indptr, csr.indices, csr.data,
         flat.left, flat.right, flat.feat, flat.thresh, flat.defl, flat.value, out,
+    )
+    return out
+
+
+# -- whole-forest prediction over CSR rows ---------------------------------------
+# Knobs of predict_forest_csr_kernel / pred_leaf_csr_kernel (values and the
+# sweep behind them: profiles/r08_sparse_predict.md). A block owns R
+# consecutive rows and every tree chunk (or tree) of them, R ~ block items /
+# chunks; a group of at most PREDICT_CSR_TILE stored entries is searched in
+# LDS, a longer one in global memory.
+PREDICT_CSR_TILE = 8192          # entries; 8 bytes each of dynamic LDS (64 KiB)
+PREDICT_CSR_BLOCK_ITEMS = 256    # (row, chunk) items a block is sized for
+_PREDICT_CSR_MAX_TILE = 8192     # PCSR_MAX_TILE in the kernel source
+
+_FLAT_DTYPES = (
+    ("left", torch.int32), ("right", torch.int32), ("feature", torch.int32),
+    ("threshold", torch.float32), ("default_left", torch.uint8), ("value", torch.float32),
+    ("tree_root", torch.int32), ("tree_cls", torch.int32),
+)
+
+
+def _rows_per_group(n_inner):
+    return max(1, PREDICT_CSR_BLOCK_ITEMS // max(1, n_inner))
+
+
+def _check_forest_csr(flat, dcsr, t_begin, t_end):
+    """Host-side validation shared by the two forest launchers; returns the
+    resolved t_end. Raises ValueError before anything is launched."""
+    if not isinstance(dcsr, DeviceCSR):
+        raise ValueError("expected a hip_sparse.DeviceCSR (upload the matrix once, predict many times)")
+    if t_end is None:
+        t_end = flat["n_trees"]
+    if not (0 <= t_begin <= t_end <= flat["n_trees"]):
+        raise ValueError(f"tree range [{t_begin}, {t_end}) out of bounds")
+    for name, t, dt in (
+        ("indptr", dcsr.indptr, torch.int64), ("indices", dcsr.indices, torch.int32),
+        ("data", dcsr.data, torch.float32),
+    ):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"device CSR {name} must be a contiguous 1-d {dt} ROCm tensor")
+    n = dcsr.shape[0]
+    if dcsr.indptr.numel() != n + 1 or dcsr.data.numel() != dcsr.indices.numel():
+        raise ValueError("device CSR arrays do not match the matrix shape")
+    for name, dt in _FLAT_DTYPES:
+        t = flat[name]
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.device != dcsr.data.device:
+            raise ValueError(f"flat forest '{name}' must be a contiguous {dt} tensor on the matrix's device")
+    if not (0 <= PREDICT_CSR_TILE <= _PREDICT_CSR_MAX_TILE):
+        raise ValueError(f"PREDICT_CSR_TILE must be within [0, {_PREDICT_CSR_MAX_TILE}] entries")
+    if t_end > t_begin:
+        max_f = int(flat["tree_max_feature"][t_begin:t_end].max())
+        if max_f >= dcsr.shape[1]:
+            raise ValueError(
+                f"the matrix has {dcsr.shape[1]} columns but the forest splits on feature {max_f}"
+            )
+    return t_end
+
+
+def predict_forest_csr(flat, dcsr, k, t_begin=0, t_end=None):
+    """(n, k) float32 summed margin contributions of trees [t_begin, t_end)
+    of a hip.make_flat_forest dict over a DeviceCSR. Equal, bit for bit, to
+    hip.predict_forest_flat on the NaN-densified rows: same (row, tree-chunk)
+    items, same tree order inside a chunk, same fixed-order chunk reduce."""
+    t_end = _check_forest_csr(flat, dcsr, t_begin, t_end)
+    k = int(k)
+    if k < 1 or (t_end > t_begin and int(flat["tree_cls_max"]) >= k):
+        raise ValueError(f"k = {k} outputs do not cover the forest's class ids")
+    n = dcsr.shape[0]
+    dev = dcsr.data.device
+    T = t_end - t_begin
+    if n == 0 or T == 0:
+        return torch.zeros((n, k), dtype=torch.float32, device=dev)
+    n_chunks, tpc = hip._predict_chunking(n, T)
+    part = torch.zeros((n_chunks, n, k), dtype=torch.float32, device=dev)
+    _K.predict_forest_csr(
+        dcsr.indptr, dcsr.indices, dcsr.data,
+        flat["left"], flat["right"], flat["feature"], flat["threshold"],
+        flat["default_left"], flat["value"], flat["tree_root"], flat["tree_cls"],
+        t_begin, t_end, part, k, n_chunks, tpc, _rows_per_group(n_chunks), PREDICT_CSR_TILE,
+    )
+    return part.sum(0) if n_chunks > 1 else part[0]
+
+
+def pred_leaf_csr(flat, dcsr, t_begin=0, t_end=None):
+    """(n, T) int32 tree-local leaf indices of trees [t_begin, t_end) over a
+    DeviceCSR; equal to hip.pred_leaf on the NaN-densified rows."""
+    t_end = _check_forest_csr(flat, dcsr, t_begin, t_end)
+    n = dcsr.shape[0]
+    T = t_end - t_begin
+    out = torch.zeros((n, T), dtype=torch.int32, device=dcsr.data.device)
+    if n == 0 or T == 0:
+        return out
+    _K.pred_leaf_csr(
+        dcsr.indptr, dcsr.indices, dcsr.data,
+        flat["left"], flat["right"], flat["feature"], flat["threshold"],
+        flat["default_left"], flat["value"], flat["tree_root"], flat["tree_cls"],
+        t_begin, t_end, out, _rows_per_group(T), PREDICT_CSR_TILE,
     )
     return out
