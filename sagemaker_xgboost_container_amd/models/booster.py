@@ -10,6 +10,7 @@ Pickled boosters (the serving pickle-first path, serve_utils.py:180-182)
 are supported via plain-numpy state.
 """
 import json
+import logging
 import os
 
 import numpy as np
@@ -27,6 +28,8 @@ MODEL_VERSION = [3, 0, 5]  # schema-compatible xgboost version
 # this much at a time.
 SPARSE_PREDICT_DENSE_BUDGET = 256 << 20
 
+logger = logging.getLogger(__name__)
+_EXPLAIN_ROUTES_LOGGED = set()
 
 
 def objective_params_from_json(obj_json, params):
@@ -207,6 +210,12 @@ class Booster:
             )
         if ntree_limit:  # legacy alias: trees -> iterations
             iteration_range = (0, int(ntree_limit) // max(1, self._trees_per_round()))
+        if pred_contribs and self._sparse_explain_route(
+            data, approx_contribs=approx_contribs, iteration_range=iteration_range
+        ):
+            if validate_features:
+                self._validate_features(data)
+            return self._pred_contribs_sparse(data, iteration_range)
         if self._sparse_predict_route(data, explain=pred_contribs or pred_interactions):
             if validate_features:
                 self._validate_features(data)
@@ -406,7 +415,10 @@ class Booster:
         pkey = "shap_paths:" + key
         if pkey not in cache:
             cache[pkey] = hip.make_shap_paths(self.trees, self.tree_info, wd, device)
-        return dict(cache[key], shap_paths=cache[pkey])
+        # compact-kernel plans and slot tables, keyed inside by device, tree
+        # range and trees_per_chunk (ops/hip.py)
+        slots = cache.setdefault("shap_slots:" + key, {})
+        return dict(cache[key], shap_paths=cache[pkey], shap_slot_cache=slots)
 
     def _explain_on_device(self, X, t_begin, t_end, shap):
         """The hip flat forest when the device kernels serve this request,
@@ -428,6 +440,108 @@ class Booster:
             if not fits or max_f >= X.shape[1]:
                 return None
         return flat
+
+    def _log_explain_route(self, route):
+        """Debug-log a contribs route the first time the process takes it."""
+        if route not in _EXPLAIN_ROUTES_LOGGED:
+            _EXPLAIN_ROUTES_LOGGED.add(route)
+            logger.debug("pred_contribs route: %s", route)
+
+    def _compact_explain_flat(self, device, n, f, t_begin, t_end):
+        """The hip flat forest when the compact TreeSHAP kernel (chunk-local
+        phi slots, ops/hip.py tree_shap_compact) can serve `n` rows of `f`
+        columns on `device`, else None: a hip device, a non-empty tree range
+        whose splits lie inside the matrix, paths that fit a wave, and slot
+        slabs that fit LDS for at least one tree per chunk."""
+        if device.type != "cuda" or not self.trees or t_end <= t_begin:
+            return None
+        hip = ops.backend_for(device)
+        if hip.NAME != "hip":
+            return None
+        flat = self._device_flat_forest(device, with_paths=True)
+        L, max_f, _ = hip.shap_limits(flat["shap_paths"], self.n_outputs, f, t_begin, t_end)
+        if L > hip.SHAP_MAX_PATH_LEN or max_f >= f:
+            return None
+        if hip.shap_compact_plan_cached(flat, f, t_begin, t_end, n) is None:
+            return None
+        return flat
+
+    def _sparse_explain_route(self, data, approx_contribs=False, pred_interactions=False,
+                              iteration_range=None):
+        """Does predict(pred_contribs=True) keep this input sparse?
+
+        Only exact contributions: approx_contribs and pred_interactions keep
+        the densifying path (an interactions result is n * (f + 1)^2, at
+        least the dense image). Yes for a sparse DMatrix holding a canonical
+        CSR on a tree booster predicting on a hip device, when the compact
+        kernel's slot tables fit. SMXGB_SPARSE_EXPLAIN=1 forces the route,
+        =0 disables it; unset, the memory rule of _sparse_predict_route
+        applies (wide and at most half full, dense float32 image beyond
+        SPARSE_PREDICT_DENSE_BUDGET). Independent of SMXGB_SPARSE_PREDICT.
+        """
+        from ..data.dmatrix import DMatrix
+
+        flag = os.environ.get("SMXGB_SPARSE_EXPLAIN")
+        if flag == "0" or approx_contribs or pred_interactions:
+            return False
+        if not isinstance(data, DMatrix) or not data.is_sparse:
+            return False
+        if self.booster_type not in ("gbtree", "dart"):
+            return False
+        device = self._predict_device()
+        if device.type != "cuda" or ops.backend_for(device).NAME != "hip":
+            return False
+        csr = data.csr()
+        n, f = csr.shape
+        if flag != "1":
+            from .trainer import sparse_auto_engage
+
+            if not sparse_auto_engage(n, f, csr.nnz):
+                return False
+            if n * f * 4 <= SPARSE_PREDICT_DENSE_BUDGET:
+                return False
+        if not csr.has_canonical_format:
+            return False
+        t_begin, t_end = self._tree_range(iteration_range)
+        return self._compact_explain_flat(device, n, f, t_begin, t_end) is not None
+
+    def _contribs_compact(self, flat, X, n, f, t_begin, t_end, base_margin):
+        """pred_contribs through the compact kernel: X is a dense device
+        tensor or a DeviceCSR. Each row tile's (rows, U) result is scattered
+        into the float32 (n, k, f+1) host array; the device never holds an
+        n x (f+1) tensor. Bias column: float32 of expected values + starting
+        margin summed in float64, as on the other routes."""
+        from ..ops import hip
+
+        k = self.n_outputs
+        out = np.zeros((n, k * (f + 1)), dtype=np.float32)
+        cols, tiles = hip.tree_shap_compact_tiles(flat, X, k, t_begin, t_end)
+        for r0, r1, phi in tiles:
+            out[r0:r1, cols] = phi.to(torch.float32).cpu().numpy()
+            del phi
+        out = out.reshape(n, k, f + 1)
+        bias = self._bias_rows(n, base_margin, torch.device("cpu"))
+        if t_end > t_begin:
+            bias = self._expected_values(t_begin, t_end).to(torch.float64).unsqueeze(0) + bias
+        out[:, :, f] = bias.to(torch.float32).numpy()
+        return out[:, 0, :] if k == 1 else out
+
+    def _pred_contribs_sparse(self, data, iteration_range):
+        """Exact contributions of a sparse DMatrix over its CSR arrays
+        (uploaded as they are): equal to the dense kernels on the
+        NaN-densified rows, without the n x f image on host or device."""
+        from ..ops import hip_sparse
+
+        csr = data.csr()
+        n, f = csr.shape
+        device = self._predict_device()
+        t_begin, t_end = self._tree_range(iteration_range)
+        flat = self._device_flat_forest(device, with_paths=True)
+        self._log_explain_route("compact kernel over CSR rows")
+        dcsr = hip_sparse.DeviceCSR(csr, device)
+        return self._contribs_compact(
+            flat, dcsr, n, f, t_begin, t_end, data.get_base_margin()
+        )
 
     def _expected_values(self, t_begin, t_end):
         """Per-class TreeSHAP bias of trees [t_begin, t_end) (cached)."""
@@ -620,7 +734,8 @@ class Booster:
         Exact TreeSHAP by default — parity with the reference's native
         pred_contribs path (reference test_abalone.py:65): the path-form
         HIP kernel when X is on the GPU and the forest is within the device
-        limits, else Lundberg's recursion in parallel C++ on the host.
+        limits (the compact-slot kernel where the dense phi slab does not
+        fit LDS), else Lundberg's recursion in parallel C++ on the host.
         `approx=True` is the Saabas approximation (xgboost's
         approx_contribs=True), vectorized over the flat forest on X's
         device. Returns (n, f+1) for single-output, (n, k, f+1) for
@@ -644,10 +759,25 @@ class Booster:
                 flat = self._cpu_flat_forest()
             phi = torch_ref.saabas_contribs(flat, X, k, t_begin, t_end)
         else:
-            flat = self._explain_on_device(X, t_begin, t_end, shap=True)
+            # SMXGB_SHAP_COMPACT: 1 = compact kernel for every device request,
+            # 0 = never; unset = only where the dense phi slab does not fit
+            # LDS (wide or multiclass models), which used to mean the host
+            compact = os.environ.get("SMXGB_SHAP_COMPACT")
+            flat = None if compact == "1" else self._explain_on_device(X, t_begin, t_end, shap=True)
+            if flat is None and compact != "0":
+                cflat = self._compact_explain_flat(X.device, n, X.shape[1], t_begin, t_end)
+                if cflat is not None:
+                    self._log_explain_route("compact kernel over dense rows")
+                    return self._contribs_compact(
+                        cflat, X, n, X.shape[1], t_begin, t_end, base_margin
+                    )
+                if compact == "1":
+                    flat = self._explain_on_device(X, t_begin, t_end, shap=True)
             if flat is not None:
+                self._log_explain_route("dense-slab kernel")
                 phi = ops.backend_for(X.device).tree_shap(flat, X, k, t_begin, t_end)
             else:
+                self._log_explain_route("host recursion")
                 phi = torch_ref.tree_shap(self._cpu_flat_forest(), X.cpu(), k, t_begin, t_end)
             if t_end > t_begin:
                 phi[:, :, -1] += self._expected_values(t_begin, t_end).to(phi.device).unsqueeze(0)

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "smxgb_jobs.h"  // WAVE, HIST_BLOCK, CHECK_GPU, HistJob / PartJob / LeafJob
+#include "smxgb_shap.h"  // SHAP_BLOCK, shap_one_fraction, shap_unwound_sum
 
 // LDS histogram layout: separate g and h arrays (SoA). A 16-B interleaved
 // (g,h) slot can only start on 8 of the 32 bank groups (measured 75% of
@@ -1561,55 +1562,8 @@ __global__ __launch_bounds__(HIST_BLOCK) void pred_leaf_kernel(
 // count (Lmax) and only the arithmetic is predicated on the path length,
 // so all W lanes of a group always execute the same cross-lane ops.
 
-#define SHAP_BLOCK 256
-#define SHAP_F_NAN 1     // missing values follow this path on this feature
-#define SHAP_F_LO 2      // path has a right turn on this feature (x >= lo)
-#define SHAP_F_HI 4      // path has a left turn on this feature  (x <  hi)
-
-__device__ inline double shap_one_fraction(float x, float lo, float hi, int flags) {
-  if (isnan(x)) return (flags & SHAP_F_NAN) ? 1.0 : 0.0;
-  const bool ok = (!(flags & SHAP_F_LO) || x >= lo) && (!(flags & SHAP_F_HI) || x < hi);
-  return ok ? 1.0 : 0.0;
-}
-
-// Lane `gl` of a W-wide group holds element gl (z, o) of a path of `len`
-// elements (element 0 = dummy root, z = o = 1). Returns the unwound
-// permutation-weight sum for this lane's element. Must be called by all W
-// lanes of the group; `lmax` (>= len, <= W) is the uniform shuffle bound.
-__device__ inline double shap_unwound_sum(double z, double o, int gl, int len, int lmax,
-                                          int W) {
-  double w = gl == 0 ? 1.0 : 0.0;
-  for (int d = 1; d < lmax; ++d) {
-    const double zd = __shfl(z, d, W);
-    const double od = __shfl(o, d, W);
-    const double wl = __shfl_up(w, 1, W);
-    if (d < len) {
-      const double inv = 1.0 / (d + 1);
-      double nw = 0.0;
-      if (gl <= d) {
-        nw = zd * w * (d - gl) * inv;
-        if (gl > 0) nw += od * wl * gl * inv;
-      }
-      w = nw;
-    }
-  }
-  const int D = len - 1;
-  double next = __shfl(w, D > 0 ? D : 0, W);
-  double total = 0.0;
-  for (int j = lmax - 2; j >= 0; --j) {
-    const double wj = __shfl(w, j, W);
-    if (j < D) {
-      if (o != 0.0) {
-        const double tmp = next * (D + 1) / ((j + 1) * o);
-        total += tmp;
-        next = wj - tmp * z * (D - j) / (double)(D + 1);
-      } else if (z != 0.0) {
-        total += (wj / z) * (D + 1) / (double)(D - j);
-      }
-    }
-  }
-  return total;
-}
+// SHAP_BLOCK, the SHAP_F_* flags, shap_one_fraction and shap_unwound_sum
+// live in smxgb_shap.h, shared with smxgb_shap_compact.hip.
 
 // out: (n_chunks, n, k, nfeat+1) fp64 partials, bias column untouched.
 // A group exclusively owns out[chunk, row, :, :] — nothing is shared
@@ -2544,10 +2498,12 @@ void find_splits(torch::Tensor hist, torch::Tensor parent, torch::Tensor nbins,
 
 void init_text_parsers(pybind11::module_& m);
 void init_sparse_kernels(pybind11::module_& m);
+void init_shap_compact_kernels(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_text_parsers(m);
   init_sparse_kernels(m);
+  init_shap_compact_kernels(m);
   m.def("hist_build", &hist_build, "batched LDS-staged fixed-point histogram build");
   m.def("hist_convert", &hist_convert, "fixed-point -> float32 histogram convert");
   m.def("partition", &partition, "batched two-ended row partition");

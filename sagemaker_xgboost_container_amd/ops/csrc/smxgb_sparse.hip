@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "smxgb_jobs.h"
+#include "smxgb_shap.h"
 
 typedef unsigned long long u64;
 
@@ -165,22 +166,7 @@ __global__ __launch_bounds__(HIST_BLOCK) void hist_sparse_close_kernel(
 // row partition
 // ---------------------------------------------------------------------------
 
-// position of `feature` among the sorted column ids [lo, hi), or -1
-__device__ inline long long csr_find(const int* __restrict__ indices, long long lo,
-                                     long long hi, int feature) {
-  while (lo < hi) {
-    const long long mid = lo + ((hi - lo) >> 1);
-    const int c = indices[mid];
-    if (c < feature) {
-      lo = mid + 1;
-    } else if (c > feature) {
-      hi = mid;
-    } else {
-      return mid;
-    }
-  }
-  return -1;
-}
+// csr_find (binary search of a row's sorted column ids): smxgb_shap.h
 
 #define SPART_TILE 4096
 

@@ -428,6 +428,8 @@ def make_shap_paths(trees, tree_info, weight_drop, device):
     dev["tree_max_len"] = host["tree_max_len"]
     dev["tree_max_feature"] = host["tree_max_feature"]
     dev["n_trees"] = len(trees)
+    # the numpy tables: make_shap_slots (compact kernel) is built from them
+    dev["host"] = host
     return dev
 
 
@@ -536,6 +538,219 @@ def tree_shap_interactions(flat, X, k, t_begin=0, t_end=None):
     diag = phi - out.sum(dim=3)
     out.diagonal(dim1=2, dim2=3).copy_(diag)
     return out
+
+
+# -- compact TreeSHAP: chunk-local phi slots, dense or CSR rows ----------------
+# shap_paths_compact_kernel keeps max_c S_c doubles per lane group in LDS
+# (S_c = distinct (class, feature) cells of chunk c), so neither f nor k
+# bounds it; see csrc/smxgb_shap_compact.hip and shap_paths.make_shap_slots.
+
+def _shap_want_tpc(n, T):
+    """trees_per_chunk _shap_tiles would pick for occupancy alone."""
+    want = max(1, (_SHAP_TARGET_GROUPS + max(n, 1) - 1) // max(n, 1))
+    n_chunks = int(min(T, want))
+    return (T + n_chunks - 1) // n_chunks
+
+
+def shap_compact_plan(paths, f, t_begin, t_end, n):
+    """(trees_per_chunk, block) for the compact kernel over `n` rows, or
+    None when the range does not fit: the largest uniform trees_per_chunk,
+    no larger than what occupancy wants, whose largest chunk keeps
+    groups_per_block * max_slots * 8 within SHAP_LDS_BUDGET. When a single
+    tree does not fit a 256-thread block the block drops to one wave
+    (64 / W groups). `paths` are the host path tables (or the device dict
+    that carries them)."""
+    from . import shap_paths as _sp
+
+    host = paths.get("host", paths)
+    T = t_end - t_begin
+    if T <= 0:
+        return None
+    L, _ = _sp.range_limits(host, t_begin, t_end)
+    if L > SHAP_MAX_PATH_LEN:
+        return None
+    W = shap_group_width(L)
+    pairs = _sp.range_pairs(host, f, t_begin, t_end)
+    one_tree = _sp.max_chunk_slots(pairs, 1)
+    want = _shap_want_tpc(n, T)
+    for block in (_SHAP_BLOCK, 64):
+        cap = SHAP_LDS_BUDGET // (8 * (block // W))
+        if one_tree > cap:
+            continue
+        for tpc in range(want, 1, -1):
+            if _sp.max_chunk_slots(pairs, tpc) <= cap:
+                return tpc, block
+        return 1, block
+    return None
+
+
+def shap_compact_plan_cached(flat, f, t_begin, t_end, n):
+    """shap_compact_plan of flat['shap_paths'], remembered in
+    flat['shap_slot_cache'] (the Booster's predict cache) when present."""
+    cache = flat.get("shap_slot_cache")
+    key = ("plan", f, t_begin, t_end, _shap_want_tpc(n, t_end - t_begin), SHAP_LDS_BUDGET)
+    if cache is not None and key in cache:
+        return cache[key]
+    plan = shap_compact_plan(flat["shap_paths"], f, t_begin, t_end, n)
+    if cache is not None:
+        cache[key] = plan
+    return plan
+
+
+def _shap_slot_tables(flat, f, t_begin, t_end, tpc, device):
+    """Slot tables of (range, trees_per_chunk) on `device`; cached in
+    flat['shap_slot_cache'] (the Booster's predict cache) when present."""
+    from . import shap_paths as _sp
+
+    cache = flat.get("shap_slot_cache")
+    key = ("slots", str(device), f, t_begin, t_end, tpc)
+    if cache is not None and key in cache:
+        return cache[key]
+    host = _sp.make_shap_slots(flat["shap_paths"]["host"], f, t_begin, t_end, tpc)
+    # content checks the launcher relies on (it sees only sizes)
+    S = int(host["slot_col"].shape[0])
+    ptr = host["chunk_slot_ptr"]
+    if (
+        ptr[0] != 0 or ptr[-1] != S or (np.diff(ptr) < 0).any()
+        or (host["elem_slot"] < 0).any()
+        or (host["elem_slot"].size and host["elem_slot"].max() >= max(host["max_slots"], 1))
+        or (host["col_slots"].size and (host["col_slots"].min() < 0 or host["col_slots"].max() >= S))
+        or host["col_ptr"][-1] != S
+    ):
+        raise ValueError("inconsistent TreeSHAP slot tables")
+    tabs = dict(host)
+    for name in ("elem_slot", "chunk_slot_ptr", "col_ptr", "col_slots"):
+        tabs[name] = torch.from_numpy(host[name]).to(device)
+    tabs["cols_dev"] = torch.from_numpy(host["cols"]).to(device)
+    tabs["S"] = S
+    if cache is not None:
+        cache[key] = tabs
+    return tabs
+
+
+def _shap_compact_prepare(flat, X, k, t_begin, t_end):
+    """Host-side validation of a compact TreeSHAP request; raises ValueError
+    before anything is launched. Returns (paths, t_end, n, f, csr, L, max_f)."""
+    from . import hip_sparse as _hs
+    from . import shap_paths as _sp
+
+    paths = flat.get("shap_paths")
+    if paths is None or "host" not in paths:
+        raise ValueError("flat forest carries no path tables (flat['shap_paths'])")
+    if t_end is None:
+        t_end = paths["n_trees"]
+    if not (0 <= t_begin <= t_end <= paths["n_trees"]):
+        raise ValueError(f"tree range [{t_begin}, {t_end}) out of bounds")
+    csr = isinstance(X, _hs.DeviceCSR)
+    if csr:
+        for name, t, dt in (
+            ("indptr", X.indptr, torch.int64), ("indices", X.indices, torch.int32),
+            ("data", X.data, torch.float32),
+        ):
+            if (
+                not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt
+                or not t.is_contiguous() or t.dim() != 1
+            ):
+                raise ValueError(f"device CSR {name} must be a contiguous 1-d {dt} ROCm tensor")
+        n, f = int(X.shape[0]), int(X.shape[1])
+        nnz = X.indices.numel()
+        if X.indptr.numel() != n + 1 or X.data.numel() != nnz:
+            raise ValueError("device CSR arrays do not match the matrix shape")
+        # offsets against the buffers: a slice's offsets need not start at 0
+        lo, hi = (int(v) for v in X.indptr[[0, -1]].tolist())
+        if not (0 <= lo <= hi <= nnz) or bool((X.indptr[1:] < X.indptr[:-1]).any()):
+            raise ValueError("device CSR offsets leave the index buffer")
+        device = X.data.device
+    else:
+        if (
+            not isinstance(X, torch.Tensor) or not X.is_cuda or X.dim() != 2
+            or X.dtype != torch.float32
+        ):
+            raise ValueError("X must be a 2-d float32 ROCm device tensor or a DeviceCSR")
+        n, f = X.shape
+        device = X.device
+    if paths["elem_feature"].device != device:
+        raise ValueError("the path tables live on another device than the matrix")
+    k = int(k)
+    host = paths["host"]
+    p0, p1 = int(host["tree_path_ptr"][t_begin]), int(host["tree_path_ptr"][t_end])
+    if k < 1 or (p1 > p0 and int(host["path_cls"][p0:p1].max()) >= k):
+        raise ValueError(f"k = {k} outputs do not cover the forest's class ids")
+    L, max_f = _sp.range_limits(host, t_begin, t_end)
+    if max_f >= f:
+        raise ValueError(f"the matrix has {f} columns but the forest splits on feature {max_f}")
+    if L > SHAP_MAX_PATH_LEN:
+        raise ValueError(f"path length {L} exceeds the device limit {SHAP_MAX_PATH_LEN}")
+    return paths, t_end, n, f, csr, L, max_f
+
+
+def tree_shap_compact_tiles(flat, X, k, t_begin=0, t_end=None):
+    """Exact TreeSHAP contributions over a dense (n, f) float32 device
+    tensor or a hip_sparse.DeviceCSR, one row tile at a time.
+
+    Returns (cols, tiles): `cols` (U,) int64 host array of the dense output
+    columns cls * (f + 1) + feature the range touches, sorted; `tiles` a
+    generator of (r0, r1, phi) with phi (r1 - r0, U) float64 on the device,
+    valid until the next tile is drawn. Rows are tiled so that the slot
+    partials rows * S * 8 stay under SHAP_PARTIAL_CAP. The bias column is
+    never produced. Everything is validated before the first launch."""
+    paths, t_end, n, f, csr, L, max_f = _shap_compact_prepare(flat, X, k, t_begin, t_end)
+    empty = np.zeros(0, dtype=np.int64)
+    if n == 0 or t_end <= t_begin or max_f < 0:
+        return empty, iter(())
+    plan = shap_compact_plan_cached(flat, f, t_begin, t_end, n)
+    if plan is None:
+        raise ValueError("slot slabs do not fit the LDS budget")
+    tpc, block = plan
+    device = X.data.device if csr else X.device
+    tabs = _shap_slot_tables(flat, f, t_begin, t_end, tpc, device)
+    S, U = tabs["S"], int(tabs["cols"].shape[0])
+    W = shap_group_width(L)
+    if not csr:
+        X = X.contiguous()
+    rows_per_tile = max(1, min(n, SHAP_PARTIAL_CAP // (S * 8)))
+    none64 = torch.empty(0, dtype=torch.int64, device=device)
+    none32 = torch.empty(0, dtype=torch.int32, device=device)
+
+    def tiles():
+        part = torch.empty((rows_per_tile, S), dtype=torch.float64, device=device)
+        for r0 in range(0, n, rows_per_tile):
+            r1 = min(n, r0 + rows_per_tile)
+            rows = r1 - r0
+            if csr:
+                args = (X.data, X.indptr[r0:r1 + 1], X.indices)
+            else:
+                args = (X[r0:r1], none64, none32)
+            _K.tree_shap_compact(
+                *args, rows, f, csr,
+                paths["elem_feature"], paths["elem_lo"], paths["elem_hi"],
+                paths["elem_flags"], paths["elem_zero_fraction"], paths["path_offset"],
+                paths["path_value"], paths["tree_path_ptr"], t_begin, t_end,
+                tabs["elem_slot"], tabs["elem_base"], tabs["chunk_slot_ptr"],
+                part[:rows], S, tabs["n_chunks"], tpc, W, L, max_f, tabs["max_slots"], block,
+            )
+            phi = torch.empty((rows, U), dtype=torch.float64, device=device)
+            _K.shap_slot_reduce(part[:rows], tabs["col_ptr"], tabs["col_slots"], phi)
+            yield r0, r1, phi
+
+    return tabs["cols"], tiles()
+
+
+def tree_shap_compact(flat, X, k, t_begin=0, t_end=None):
+    """Exact TreeSHAP contributions in compact form: (phi, cols) with phi
+    (n, U) float64 on the device and cols (U,) int64 the dense output columns
+    cls * (f + 1) + feature, sorted. Columns the tree range never splits on
+    are absent (their contribution is zero); the bias column is NOT filled
+    (same contract as tree_shap). X is a dense float32 device tensor or a
+    hip_sparse.DeviceCSR, where an absent entry is a missing value."""
+    cols, tiles = tree_shap_compact_tiles(flat, X, k, t_begin, t_end)
+    csr = not isinstance(X, torch.Tensor)
+    device = X.data.device if csr else X.device
+    n = int(X.shape[0])
+    phi = torch.empty((n, cols.shape[0]), dtype=torch.float64, device=device)
+    for r0, r1, tile in tiles:
+        phi[r0:r1] = tile
+    return phi, torch.from_numpy(cols).to(device)
 
 
 def pred_leaf(flat, X, t_begin=0, t_end=None):

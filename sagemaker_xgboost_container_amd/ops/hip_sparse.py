@@ -27,7 +27,11 @@ loops unchanged. Kernels: csrc/smxgb_sparse.hip.
   groups search global memory. The (row, tree-chunk) items, the tree order
   inside a chunk and the fixed-order chunk reduce are the dense kernel's, so
   the results equal hip.predict_forest_flat / hip.pred_leaf on the
-  NaN-densified rows bit for bit. TreeSHAP over CSR is not implemented.
+  NaN-densified rows bit for bit.
+* exact TreeSHAP contributions over a DeviceCSR: hip.tree_shap_compact (the
+  compact-slot kernel of csrc/smxgb_shap_compact.hip with a binary-search
+  row accessor), bit-equal to its dense accessor on the NaN-densified rows.
+  Interaction values over CSR are not implemented.
 
 There is no DeviceGrower for this layout: HistGrower.grow_path stays
 "per_level", which mirrors the device grower's float32 node arithmetic

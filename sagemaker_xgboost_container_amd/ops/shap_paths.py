@@ -119,6 +119,102 @@ def make_shap_paths(trees, tree_info, weight_drop):
     }
 
 
+def _range_elements(paths, f, t_begin, t_end):
+    """Per path element of trees [t_begin, t_end): (first element id, tree
+    index relative to t_begin, dense output column path_cls * (f + 1) +
+    elem_feature), the last two as int64 arrays."""
+    tree_ptr = paths["tree_path_ptr"]
+    p0, p1 = int(tree_ptr[t_begin]), int(tree_ptr[t_end])
+    off = paths["path_offset"]
+    e0, e1 = int(off[p0]), int(off[p1])
+    lens = np.diff(off[p0:p1 + 1]).astype(np.int64)
+    tree = np.repeat(paths["path_tree"][p0:p1].astype(np.int64) - t_begin, lens)
+    col = (
+        np.repeat(paths["path_cls"][p0:p1].astype(np.int64), lens) * (f + 1)
+        + paths["elem_feature"][e0:e1].astype(np.int64)
+    )
+    return e0, tree, col
+
+
+def range_pairs(paths, f, t_begin, t_end):
+    """Distinct (tree, column) pairs of trees [t_begin, t_end): two int64
+    arrays (tree - t_begin, dense output column) sorted by tree, then
+    column. There are at most as many as the range has split nodes."""
+    _, tree, col = _range_elements(paths, f, t_begin, t_end)
+    width = int(col.max()) + 1 if col.size else 1
+    uniq = np.unique(tree * width + col)
+    return uniq // width, uniq % width
+
+
+def max_chunk_slots(pairs, trees_per_chunk):
+    """max_c S_c of a uniform chunking, from range_pairs' output alone."""
+    tree, col = pairs
+    if tree.size == 0:
+        return 0
+    width = int(col.max()) + 1
+    uniq = np.unique((tree // trees_per_chunk) * width + col)
+    return int(np.bincount(uniq // width).max())
+
+
+def make_shap_slots(paths, f, t_begin, t_end, trees_per_chunk):
+    """Chunk-local phi slots of trees [t_begin, t_end) cut into chunks of
+    `trees_per_chunk` trees (the last one may be short).
+
+    Within a chunk every distinct (path_cls, elem_feature) pair gets one slot
+    0 .. S_c-1, in ascending order of its dense output column
+    cls * (f + 1) + feature. Returns a dict of numpy arrays and ints:
+      elem_slot       int32, one per path element of the range (element ids
+                      elem_base .. elem_base + len - 1): its chunk-local slot
+      elem_base       first element id of the range
+      chunk_slot_ptr  (C+1,) int32 offsets of the chunks' slots in the ragged
+                      slot axis of length S = sum S_c
+      slot_col        (S,) int64 dense output column of every ragged slot
+      cols            (U,) int64 sorted distinct values of slot_col
+      col_ptr         (U+1,) int32 and
+      col_slots       (S,) int32: the ragged slots of cols[j], in ascending
+                      chunk order, are col_slots[col_ptr[j]:col_ptr[j+1]]
+      max_slots       max_c S_c (0 when no tree of the range splits)
+      n_chunks, trees_per_chunk
+    """
+    if trees_per_chunk < 1:
+        raise ValueError("trees_per_chunk must be at least 1")
+    n_trees = len(paths["tree_path_ptr"]) - 1
+    if not (0 <= t_begin <= t_end <= n_trees):
+        raise ValueError(f"tree range [{t_begin}, {t_end}) out of bounds")
+    T = t_end - t_begin
+    C = (T + trees_per_chunk - 1) // trees_per_chunk
+    e0, tree, col = _range_elements(paths, f, t_begin, t_end)
+    chunk = tree // trees_per_chunk
+    width = int(col.max()) + 1 if col.size else 1
+    # ragged slot axis: distinct (chunk, column) pairs, chunk-major
+    uniq, inverse = np.unique(chunk * width + col, return_inverse=True)
+    slot_chunk = uniq // width
+    slot_col = uniq % width
+    S = int(uniq.shape[0])
+    if S >= 2 ** 31:
+        raise ValueError("slot axis does not fit int32 offsets")
+    chunk_slot_ptr = np.zeros(C + 1, dtype=np.int64)
+    np.cumsum(np.bincount(slot_chunk, minlength=C), out=chunk_slot_ptr[1:])
+    elem_slot = inverse.reshape(-1).astype(np.int64) - chunk_slot_ptr[chunk]
+    # per output column: its slots, ascending ragged index = ascending chunk
+    col_slots = np.argsort(slot_col, kind="stable")
+    cols, counts = np.unique(slot_col, return_counts=True)
+    col_ptr = np.zeros(cols.shape[0] + 1, dtype=np.int64)
+    np.cumsum(counts, out=col_ptr[1:])
+    return {
+        "elem_slot": elem_slot.astype(np.int32),
+        "elem_base": e0,
+        "chunk_slot_ptr": chunk_slot_ptr.astype(np.int32),
+        "slot_col": slot_col.astype(np.int64),
+        "cols": cols.astype(np.int64),
+        "col_ptr": col_ptr.astype(np.int32),
+        "col_slots": col_slots.astype(np.int32),
+        "max_slots": int(np.diff(chunk_slot_ptr).max()) if C else 0,
+        "n_chunks": C,
+        "trees_per_chunk": int(trees_per_chunk),
+    }
+
+
 def range_limits(paths, t_begin, t_end):
     """(L, max_feature) of trees [t_begin, t_end): the longest path incl.
     the dummy root element, and the largest split feature (-1 if none)."""
