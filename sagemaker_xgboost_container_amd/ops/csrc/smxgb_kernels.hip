@@ -1773,16 +1773,51 @@ void leaf_update(torch::Tensor buf0, torch::Tensor buf1, torch::Tensor margin_ba
                      (const LeafJob*)jobs.data_ptr<int>(), block_job.data_ptr<int>(), col_stride);
 }
 
+#define CHECK_GPU_DENSE(x, dt)                                                          \
+  TORCH_CHECK_VALUE(x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt,          \
+                    #x " must be a contiguous ROCm device tensor of the expected dtype")
+
+// Everything is checked on the host before the launch: a matrix narrower
+// than the widest split feature, a class id beyond k or a tree range past
+// the forest would otherwise index device memory out of bounds.
 void predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                     torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                     torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
-                    int64_t t_begin, int64_t t_end, torch::Tensor out, int64_t k,
-                    int64_t n_chunks, int64_t trees_per_chunk) {
-  CHECK_GPU(X);
+                    int64_t t_begin, int64_t t_end, int64_t max_feature, int64_t tree_cls_max,
+                    torch::Tensor out, int64_t k, int64_t n_chunks, int64_t trees_per_chunk) {
+  CHECK_GPU_DENSE(X, torch::kFloat32);
+  CHECK_GPU_DENSE(left, torch::kInt32);
+  CHECK_GPU_DENSE(right, torch::kInt32);
+  CHECK_GPU_DENSE(feat, torch::kInt32);
+  CHECK_GPU_DENSE(thresh, torch::kFloat32);
+  CHECK_GPU_DENSE(defl, torch::kUInt8);
+  CHECK_GPU_DENSE(value, torch::kFloat32);
+  CHECK_GPU_DENSE(tree_root, torch::kInt32);
+  CHECK_GPU_DENSE(tree_cls, torch::kInt32);
+  CHECK_GPU_DENSE(out, torch::kFloat32);
+  TORCH_CHECK_VALUE(X.dim() == 2, "X must be (n, f)");
+  const long long nodes = left.numel();
+  TORCH_CHECK_VALUE(right.numel() == nodes && feat.numel() == nodes && thresh.numel() == nodes &&
+                        defl.numel() == nodes && value.numel() == nodes,
+                    "forest node arrays differ in size");
+  TORCH_CHECK_VALUE(tree_cls.numel() == tree_root.numel(), "tree_root and tree_cls differ in size");
+  TORCH_CHECK_VALUE(0 <= t_begin && t_begin <= t_end && t_end <= tree_root.numel(),
+                    "tree range out of bounds");
   const long long n = X.size(0);
+  const long long T = t_end - t_begin;
+  TORCH_CHECK_VALUE(k >= 1 && n_chunks >= 1 && trees_per_chunk >= 1 &&
+                        n_chunks * trees_per_chunk >= T &&
+                        n_chunks * trees_per_chunk <= (1ll << 30) && t_end <= (1ll << 30),
+                    "tree chunking does not cover the tree range");
+  TORCH_CHECK_VALUE(out.numel() == n_chunks * n * k, "out must be (n_chunks, n, k)");
+  TORCH_CHECK_VALUE(T == 0 || (0 <= tree_cls_max && tree_cls_max < k), "the forest holds class id ",
+                    tree_cls_max, " but k is ", k);
+  TORCH_CHECK_VALUE(T == 0 || max_feature < X.size(1), "X has ", X.size(1),
+                    " columns but the forest splits on feature ", max_feature);
+  if (n == 0 || T == 0) return;
   const long long total = n * n_chunks;
   const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 4096);
-  hipLaunchKernelGGL(predict_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0, current_stream(),
+  hipLaunchKernelGGL(predict_kernel, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
                      X.data_ptr<float>(), n, (int)X.size(1), left.data_ptr<int>(),
                      right.data_ptr<int>(), feat.data_ptr<int>(), thresh.data_ptr<float>(),
                      defl.data_ptr<unsigned char>(), value.data_ptr<float>(),
@@ -1790,10 +1825,6 @@ void predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                      (int)t_begin, (int)t_end, out.data_ptr<float>(), (int)k, (int)n_chunks,
                      (int)trees_per_chunk);
 }
-
-#define CHECK_GPU_DENSE(x, dt)                                                          \
-  TORCH_CHECK_VALUE(x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt,          \
-                    #x " must be a contiguous ROCm device tensor of the expected dtype")
 
 void pred_leaf(torch::Tensor X, torch::Tensor left, torch::Tensor right, torch::Tensor feat,
                torch::Tensor thresh, torch::Tensor defl, torch::Tensor tree_root,
@@ -2462,10 +2493,27 @@ void grow_tree_enqueue(
   }
 }
 
+// `pmax` / `psum` hold one (|g|, |h|) maximum and one (g, h) sum per block:
+// their first dimension is the grid size.
 void grad_fused(torch::Tensor margin, torch::Tensor y, torch::Tensor w, torch::Tensor gh,
                 torch::Tensor pmax, torch::Tensor psum, int64_t mode, double spw) {
-  CHECK_GPU(margin);
+  CHECK_GPU_DENSE(margin, torch::kFloat32);
+  CHECK_GPU_DENSE(y, torch::kFloat32);
+  CHECK_GPU_DENSE(w, torch::kFloat32);
+  CHECK_GPU_DENSE(gh, torch::kFloat32);
+  CHECK_GPU_DENSE(pmax, torch::kFloat32);
+  CHECK_GPU_DENSE(psum, torch::kFloat64);
   const long long n = margin.numel();
+  TORCH_CHECK_VALUE(y.numel() == n, "y holds ", y.numel(), " labels for ", n, " margins");
+  TORCH_CHECK_VALUE(w.numel() == 0 || w.numel() == n, "w holds ", w.numel(), " weights for ", n,
+                    " margins");
+  TORCH_CHECK_VALUE(gh.numel() == 2 * n, "gh must be (n, 2)");
+  TORCH_CHECK_VALUE(pmax.dim() == 2 && pmax.size(1) == 2 && pmax.size(0) >= 1 &&
+                        pmax.size(0) <= 65536,
+                    "pmax must be (grid, 2)");
+  TORCH_CHECK_VALUE(psum.dim() == 2 && psum.size(1) == 2 && psum.size(0) == pmax.size(0),
+                    "psum must be (grid, 2) like pmax");
+  TORCH_CHECK_VALUE(mode == 0 || mode == 1, "mode must be 0 (logistic) or 1 (squared error)");
   const int grid = (int)pmax.size(0);
   hipLaunchKernelGGL(grad_fused_kernel, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
                      margin.data_ptr<float>(), y.data_ptr<float>(),

@@ -156,12 +156,51 @@ std::vector<torch::Tensor> parse_libsvm(const std::string& text, int64_t nthread
   return {values, indices, indptr, labels, weights, qids, ncol};
 }
 
+// Host twins of the device launchers' argument checks: a matrix narrower
+// than the widest split feature would be read past the end of its rows.
+#define CHECK_HOST_DENSE(x, dt)                                                         \
+  TORCH_CHECK_VALUE(!x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt,         \
+                    #x " must be a contiguous host tensor of the expected dtype")
+
+static void check_forest_cpu(const torch::Tensor& X, const torch::Tensor& left,
+                             const torch::Tensor& right, const torch::Tensor& feat,
+                             const torch::Tensor& thresh, const torch::Tensor& defl,
+                             const torch::Tensor& tree_root, int64_t t_begin, int64_t t_end,
+                             int64_t max_feature) {
+  CHECK_HOST_DENSE(X, torch::kFloat32);
+  CHECK_HOST_DENSE(left, torch::kInt32);
+  CHECK_HOST_DENSE(right, torch::kInt32);
+  CHECK_HOST_DENSE(feat, torch::kInt32);
+  CHECK_HOST_DENSE(thresh, torch::kFloat32);
+  CHECK_HOST_DENSE(defl, torch::kUInt8);
+  CHECK_HOST_DENSE(tree_root, torch::kInt32);
+  TORCH_CHECK_VALUE(X.dim() == 2, "X must be (n, f)");
+  const int64_t nodes = left.numel();
+  TORCH_CHECK_VALUE(right.numel() == nodes && feat.numel() == nodes && thresh.numel() == nodes &&
+                        defl.numel() == nodes,
+                    "forest node arrays differ in size");
+  TORCH_CHECK_VALUE(0 <= t_begin && t_begin <= t_end && t_end <= tree_root.numel(),
+                    "tree range out of bounds");
+  TORCH_CHECK_VALUE(t_end == t_begin || max_feature < X.size(1), "X has ", X.size(1),
+                    " columns but the forest splits on feature ", max_feature);
+}
+
 // Batched forest traversal on host (serving without a GPU): parallel over
 // rows via at::parallel_for (respects torch.set_num_threads / nthread HP).
 void predict_forest_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                         torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                         torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
-                        int64_t t_begin, int64_t t_end, torch::Tensor out, int64_t k) {
+                        int64_t t_begin, int64_t t_end, int64_t max_feature,
+                        int64_t tree_cls_max, torch::Tensor out, int64_t k) {
+  check_forest_cpu(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end, max_feature);
+  CHECK_HOST_DENSE(value, torch::kFloat32);
+  CHECK_HOST_DENSE(tree_cls, torch::kInt32);
+  CHECK_HOST_DENSE(out, torch::kFloat32);
+  TORCH_CHECK_VALUE(value.numel() == left.numel(), "forest node arrays differ in size");
+  TORCH_CHECK_VALUE(tree_cls.numel() == tree_root.numel(), "tree_root and tree_cls differ in size");
+  TORCH_CHECK_VALUE(k >= 1 && out.numel() == X.size(0) * k, "out must be (n, k)");
+  TORCH_CHECK_VALUE(t_end == t_begin || (0 <= tree_cls_max && tree_cls_max < k),
+                    "the forest holds class id ", tree_cls_max, " but k is ", k);
   const float* x = X.data_ptr<float>();
   const int64_t n = X.size(0);
   const int64_t nf = X.size(1);
@@ -507,7 +546,10 @@ void tree_shap_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
 void pred_leaf_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                    torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                    torch::Tensor tree_root, int64_t t_begin, int64_t t_end,
-                   torch::Tensor out) {
+                   int64_t max_feature, torch::Tensor out) {
+  check_forest_cpu(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end, max_feature);
+  CHECK_HOST_DENSE(out, torch::kInt32);
+  TORCH_CHECK_VALUE(out.numel() == X.size(0) * (t_end - t_begin), "out must be (n, T)");
   const float* x = X.data_ptr<float>();
   const int64_t n = X.size(0);
   const int64_t nf = X.size(1);

@@ -298,6 +298,8 @@ class _FlatForest:
         self.value = torch.from_numpy(np.concatenate([t.value for t in trees]).astype(np.float32)).to(device)
         self.tree_root = torch.from_numpy(offsets[:-1]).to(device)
         self.tree_cls = torch.from_numpy(np.asarray(tree_info, dtype=np.int32)).to(device)
+        self.tree_max_feature = torch_ref.tree_max_feature(trees)
+        self.tree_cls_max = int(max(tree_info, default=0))
         self.n_trees = len(trees)
 
 
@@ -313,24 +315,27 @@ def _predict_chunking(n, T):
 
 
 def _run_predict(X, fl, k, t_begin, t_end):
+    """Check the arguments on the host (torch_ref.check_predict_args: tree
+    range, class ids, width of X), then launch; nothing is launched for a
+    refused or an empty request."""
+    max_f = torch_ref.check_predict_args(fl, X, k, t_begin, t_end)
+    if not X.is_cuda:
+        raise ValueError("X must be a 2-d float32 ROCm device tensor")
     n = X.shape[0]
     T = t_end - t_begin
+    if T == 0 or n == 0:
+        return torch.zeros((n, k), dtype=torch.float32, device=X.device)
     n_chunks, tpc = _predict_chunking(n, T)
-    if n_chunks > 1:
-        part = torch.zeros((n_chunks, n, k), dtype=torch.float32, device=X.device)
-        _K.predict_forest(
-            X.contiguous(), fl["left"], fl["right"], fl["feature"], fl["threshold"],
-            fl["default_left"], fl["value"], fl["tree_root"], fl["tree_cls"],
-            t_begin, t_end, part.reshape(-1, k), k, n_chunks, tpc,
-        )
-        return part.sum(0)  # fixed-order reduce: deterministic
-    out = torch.zeros((n, k), dtype=torch.float32, device=X.device)
+    if n_chunks == 1:
+        tpc = T
+    out = torch.zeros((n_chunks, n, k), dtype=torch.float32, device=X.device)
     _K.predict_forest(
         X.contiguous(), fl["left"], fl["right"], fl["feature"], fl["threshold"],
         fl["default_left"], fl["value"], fl["tree_root"], fl["tree_cls"],
-        t_begin, t_end, out, k, 1, T,
+        t_begin, t_end, max_f, int(fl["tree_cls_max"]), out, k, n_chunks, tpc,
     )
-    return out
+    # fixed-order reduce over the chunk axis: deterministic
+    return out.sum(0) if n_chunks > 1 else out[0]
 
 
 def predict_forest(trees, tree_info, X, k, t_begin=0, t_end=None, out=None):
@@ -342,6 +347,8 @@ def predict_forest(trees, tree_info, X, k, t_begin=0, t_end=None, out=None):
         "left": forest.left, "right": forest.right, "feature": forest.feat,
         "threshold": forest.thresh, "default_left": forest.defl, "value": forest.value,
         "tree_root": forest.tree_root, "tree_cls": forest.tree_cls,
+        "tree_max_feature": forest.tree_max_feature, "tree_cls_max": forest.tree_cls_max,
+        "n_trees": forest.n_trees,
     }
     res = _run_predict(X, fl, k, t_begin, t_end)
     if out is not None:
@@ -377,12 +384,9 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
         "cover": torch.from_numpy(
             np.concatenate([np.asarray(t.sum_hess, dtype=np.float32) for t in trees])
         ).to(device),
-        # largest split feature per tree (-1 for a stump): lets the leaf
-        # launcher reject a too-narrow X without a device round trip
-        "tree_max_feature": np.asarray(
-            [int(t.feature[t.left >= 0].max()) if (t.left >= 0).any() else -1 for t in trees],
-            dtype=np.int64,
-        ),
+        # largest split feature per tree (-1 for a stump): lets the forest
+        # launchers reject a too-narrow X without a device round trip
+        "tree_max_feature": torch_ref.tree_max_feature(trees),
         # largest class id: the CSR forest launcher checks it against k
         "tree_cls_max": int(max(tree_info, default=0)),
         "n_trees": len(trees),
@@ -390,10 +394,10 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
 
 
 def predict_forest_flat(flat, X, k, t_begin=0, t_end=None):
+    """(n, k) float32 summed margins of trees [t_begin, t_end) of a
+    make_flat_forest dict over the dense float32 device matrix X."""
     if t_end is None:
         t_end = flat["n_trees"]
-    if t_end <= t_begin:
-        return torch.zeros((X.shape[0], k), dtype=torch.float32, device=X.device)
     return _run_predict(X, flat, k, t_begin, t_end)
 
 

@@ -232,6 +232,37 @@ def predict_tree(tree, X):
     return value[node]
 
 
+def tree_max_feature(trees):
+    """Largest split feature per tree (-1 for a stump), on the host: lets an
+    entry point reject a too-narrow X before any row is read."""
+    import numpy as np
+
+    out = []
+    for t in trees:
+        internal = np.asarray(t.left) >= 0
+        out.append(int(np.asarray(t.feature)[internal].max()) if internal.any() else -1)
+    return np.asarray(out, dtype=np.int64)
+
+
+def check_predict_args(flat, X, k, t_begin, t_end, classes=True):
+    """Refuse, before any row is read, a tree range outside the forest, a
+    class id beyond k and a matrix narrower than the widest split feature of
+    the range. Returns that feature (-1: the range holds no split).
+    `classes=False` for outputs without a class axis (leaf ids)."""
+    if not (0 <= t_begin <= t_end <= flat["n_trees"]):
+        raise ValueError(f"tree range [{t_begin}, {t_end}) out of bounds")
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError("X must be a 2-d float32 tensor")
+    if classes and (k < 1 or (t_end > t_begin and int(flat["tree_cls_max"]) >= k)):
+        raise ValueError(f"the forest holds class id {flat['tree_cls_max']} but k is {k}")
+    max_f = int(flat["tree_max_feature"][t_begin:t_end].max()) if t_end > t_begin else -1
+    if max_f >= X.shape[1]:
+        raise ValueError(
+            f"X has {X.shape[1]} columns but the forest splits on feature {max_f}"
+        )
+    return max_f
+
+
 def make_flat_forest(trees, tree_info, weight_drop, device):
     """Flatten trees into device arrays with global node ids; leaf values
     pre-scaled by weight_drop (dart)."""
@@ -255,12 +286,15 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
         ).to(device),
         "tree_root": torch.from_numpy(offsets[:-1].astype(np.int64)).to(device),
         "tree_cls": torch.from_numpy(np.asarray(tree_info, dtype=np.int64)).to(device),
+        # host-side limits, checked before a traversal reads any row
+        "tree_max_feature": tree_max_feature(trees),
+        "tree_cls_max": int(max(tree_info, default=0)),
         "max_depth": max((t.max_depth() for t in trees), default=0),
         "n_trees": len(trees),
     }
 
 
-def _native_predict(flat, X, k, t_begin, t_end):
+def _native_predict(flat, X, k, t_begin, t_end, max_f):
     """Parallel C++ traversal (serving hot path on CPU hosts)."""
     from . import _smxgb_hip as K
 
@@ -278,7 +312,8 @@ def _native_predict(flat, X, k, t_begin, t_end):
     K.predict_forest_cpu(
         X.contiguous(), f["left"], f["right"], f["feature"],
         flat["threshold"].contiguous(), f["default_left"], flat["value"].contiguous(),
-        f["tree_root"], f["tree_cls"], t_begin, t_end, out, k,
+        f["tree_root"], f["tree_cls"], t_begin, t_end, max_f, int(flat["tree_cls_max"]),
+        out, k,
     )
     return out
 
@@ -288,6 +323,7 @@ def predict_forest_flat(flat, X, k, t_begin=0, t_end=None):
     traversal when the extension is built, else vectorized torch."""
     if t_end is None:
         t_end = flat["n_trees"]
+    max_f = check_predict_args(flat, X, k, t_begin, t_end)
     n = X.shape[0]
     T = t_end - t_begin
     out = torch.zeros((n, k), dtype=torch.float32, device=X.device)
@@ -295,7 +331,7 @@ def predict_forest_flat(flat, X, k, t_begin=0, t_end=None):
         return out
     if X.device.type == "cpu":
         try:
-            return _native_predict(flat, X, k, t_begin, t_end)
+            return _native_predict(flat, X, k, t_begin, t_end, max_f)
         except ImportError:
             pass
     node = flat["tree_root"][t_begin:t_end].unsqueeze(0).expand(n, T).contiguous()
@@ -696,6 +732,7 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
     if t_end is None:
         t_end = flat["n_trees"]
     X = X.cpu().contiguous()
+    max_f = check_predict_args(flat, X, 1, t_begin, t_end, classes=False)
     n = X.shape[0]
     T = t_end - t_begin
     out = torch.zeros((n, T), dtype=torch.int32)
@@ -708,7 +745,7 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
         K.pred_leaf_cpu(
             X, i32["left"], i32["right"], i32["feature"],
             flat["threshold"].contiguous(), i32["default_left"],
-            i32["tree_root"], t_begin, t_end, out,
+            i32["tree_root"], t_begin, t_end, max_f, out,
         )
         return out
     except ImportError:

@@ -351,6 +351,176 @@ class TestFusedGradients:
         m = torch.randn(100, device="cuda")
         assert hip_ops.fused_gradients("binary:hinge", m, m) is None
 
+    # saturation edges of the fp32 sigmoid: expf overflow (|m| >= 89), p
+    # rounding to 1 (m >= 17) or to a denormal-sized value, the hessian floor
+    _EDGE_MARGINS = [0.0, 1e-8, -1e-8, 16.0, -16.0, 17.0, -17.0, 30.0, -30.0, 87.0, -87.0,
+                     89.0, -89.0, 104.0, -104.0, 1e4, -1e4, float("inf"), float("-inf")]
+    # 2048 * 256 + 1: the first length past one grid-stride pass of the grid
+    _EDGE_LENGTHS = [1, 255, 256, 257, 2048 * 256 + 1]
+
+    @classmethod
+    def _edge_inputs(cls, name, n, weighted, seed):
+        """Every other element cycles through the edge margins (starting at a
+        seed-dependent one, so n = 1 meets several), the rest is N(0, 3)."""
+        rng = np.random.default_rng(seed)
+        margin = (rng.normal(size=n) * 3).astype(np.float32)
+        edges = np.asarray(cls._EDGE_MARGINS, dtype=np.float32)
+        at = np.arange(0, n, 2)
+        margin[at] = edges[(at // 2 + seed) % edges.size]
+        if name == "reg:squarederror":
+            y = rng.normal(size=n).astype(np.float32)
+        elif name == "reg:logistic":
+            y = rng.choice(np.asarray([0.0, 0.25, 0.5, 1.0], dtype=np.float32), size=n)
+        else:
+            y = rng.integers(0, 2, size=n).astype(np.float32)
+        w = (rng.random(size=n) + 0.5).astype(np.float32) if weighted else None
+        return margin, y, w
+
+    @staticmethod
+    def _oracle(name, margin, y, w, spw):
+        """The kernel's contract in float64 numpy on the float32 inputs."""
+        m = margin.astype(np.float64)
+        y64 = y.astype(np.float64)
+        if name == "reg:squarederror":
+            g, h = m - y64, np.ones_like(m)
+        else:
+            with np.errstate(over="ignore"):
+                p = 1.0 / (1.0 + np.exp(-m))
+            g = p - y64
+            h = np.maximum(p * (1.0 - p), 1e-16)
+            pos = y == np.float32(1.0)  # scale_pos_weight: exact positives only
+            g[pos] *= spw
+            h[pos] *= spw
+        if w is not None:
+            g, h = g * w.astype(np.float64), h * w.astype(np.float64)
+        return np.stack([g, h], axis=1)
+
+    @pytest.mark.parametrize("n", _EDGE_LENGTHS)
+    @pytest.mark.parametrize("spw,weighted", [(1.0, False), (3.5, True)])
+    @pytest.mark.parametrize(
+        "name", ["binary:logistic", "reg:logistic", "binary:logitraw", "reg:squarederror"]
+    )
+    def test_edges_match_float64_oracle(self, name, spw, weighted, n):
+        from sagemaker_xgboost_container_amd.ops import hip as hip_ops
+
+        seed = 17 * n + int(weighted)
+        margin, y, w = self._edge_inputs(name, n, weighted, seed % 1000)
+        dev = lambda a: None if a is None else torch.from_numpy(a).cuda()  # noqa: E731
+        gh = hip_ops.fused_gradients(name, dev(margin), dev(y), dev(w), spw)
+        assert gh is not None and gh.shape == (n, 2) and gh.dtype == torch.float32
+        torch.cuda.synchronize()
+        got = gh.cpu().numpy()
+        want = self._oracle(name, margin, y, w, spw)
+        w32 = np.ones(n, dtype=np.float32) if w is None else w
+
+        if name == "reg:squarederror":
+            # one fp32 subtraction and one multiply: bit-equal to numpy. An
+            # infinite margin has an infinite gradient; everything else is finite
+            g32 = margin - y
+            ref = np.stack([g32 * w32 if weighted else g32, w32], axis=1)
+            assert np.array_equal(got, ref)
+            assert np.isfinite(got[np.isfinite(margin)]).all()
+            finite = np.isfinite(margin)
+            err = np.abs(got[finite].astype(np.float64) - want[finite])
+            print(f"{name} weighted={weighted} n={n}: max |err| vs float64 {err.max(initial=0):.3e}")
+        else:
+            assert np.isfinite(got).all()
+            scale = (w32.astype(np.float64) * max(1.0, spw))[:, None]
+            err = np.abs(got.astype(np.float64) - want)
+            excess = err - (2e-6 * scale + 2e-5 * np.abs(want))
+            worst = int(np.argmax(excess.max(axis=1)))
+            print(f"{name} spw={spw} weighted={weighted} n={n}: max |err| g {err[:, 0].max():.3e} "
+                  f"h {err[:, 1].max():.3e}; worst row m={margin[worst]!r} y={y[worst]!r}")
+            assert (excess <= 0).all(), (
+                f"m={margin[worst]!r} y={y[worst]!r} w={w32[worst]!r}: got {got[worst]}, "
+                f"oracle {want[worst]}"
+            )
+            # the hessian floor survives scale_pos_weight and the weight
+            factor = np.where(y == np.float32(1.0), np.float32(spw), np.float32(1.0))
+            floor = np.float32(1e-16) * factor.astype(np.float32)
+            floor = floor * w32 if weighted else floor
+            assert (got[:, 1] >= floor).all()
+            if spw == 1.0 and not weighted:
+                # fp32 saturation: 1 + exp(-17) rounds to 1, exp(89) overflows
+                p = got[:, 0] + y
+                exact = (y == 0) | (y == 1)
+                assert (p[(margin >= 17) & exact] == 1.0).all()
+                assert (p[(margin <= -89) & exact] == 0.0).all()
+                assert (got[margin <= -89, 1] == np.float32(1e-16)).all()
+                assert (got[margin >= 1e4, 1] == np.float32(1e-16)).all()
+
+        # the attached maxima and sums are those of the kernel's own output
+        assert torch.equal(gh._smxgb_absmax, gh.abs().amax(dim=0))
+        torch.testing.assert_close(
+            gh._smxgb_rootsum, gh.to(torch.float64).sum(0), rtol=1e-10, atol=1e-8, equal_nan=True
+        )
+        if name != "reg:squarederror":
+            assert bool(torch.isfinite(gh._smxgb_rootsum).all())
+
+    def test_fractional_labels_get_no_scale_pos_weight(self):
+        from sagemaker_xgboost_container_amd.ops import hip as hip_ops
+
+        margin = torch.tensor([0.5, 0.5, 0.5, -2.0], device="cuda")
+        y = torch.tensor([1.0, 0.5, 0.25, 0.99999994], device="cuda")
+        plain = hip_ops.fused_gradients("reg:logistic", margin, y, None, 1.0).cpu()
+        scaled = hip_ops.fused_gradients("reg:logistic", margin, y, None, 3.5).cpu()
+        assert torch.equal(scaled[0], plain[0] * 3.5)
+        assert torch.equal(scaled[1:], plain[1:])
+
+    def test_launcher_refuses_malformed_arguments(self):
+        """Every refusal is a ValueError on the host: a short y or w never
+        reaches the kernel."""
+        from sagemaker_xgboost_container_amd.ops import hip as hip_ops
+
+        n, grid = 1000, hip_ops._GRAD_GRID
+        f32 = dict(dtype=torch.float32, device="cuda")
+        good = {
+            "margin": torch.zeros(n, **f32), "y": torch.zeros(n, **f32),
+            "w": torch.ones(n, **f32), "gh": torch.full((n, 2), -7.0, **f32),
+            "pmax": torch.zeros((grid, 2), **f32),
+            "psum": torch.zeros((grid, 2), dtype=torch.float64, device="cuda"),
+        }
+
+        def launch(mode=0, **swap):
+            a = dict(good, **swap)
+            hip_ops._K.grad_fused(a["margin"], a["y"], a["w"], a["gh"], a["pmax"], a["psum"],
+                                  mode, 1.0)
+
+        bad = {
+            "short y": dict(y=good["y"][:-1].contiguous()),
+            "long y": dict(y=torch.zeros(n + 1, **f32)),
+            "short w": dict(w=good["w"][:-1].contiguous()),
+            "gh of another size": dict(gh=torch.zeros((n - 1, 2), **f32)),
+            "pmax of another shape": dict(pmax=torch.zeros((grid, 1), **f32)),
+            "psum of another size": dict(psum=torch.zeros((grid - 1, 2), dtype=torch.float64,
+                                                          device="cuda")),
+            "float32 psum": dict(psum=torch.zeros((grid, 2), **f32)),
+            "float64 margin": dict(margin=good["margin"].double()),
+            "float64 y": dict(y=good["y"].double()),
+            "float64 w": dict(w=good["w"].double()),
+            "host y": dict(y=good["y"].cpu()),
+            "host margin": dict(margin=good["margin"].cpu()),
+            "strided margin": dict(margin=torch.zeros(2 * n, **f32)[::2]),
+            "strided y": dict(y=torch.zeros(2 * n, **f32)[::2]),
+        }
+        for what, swap in bad.items():
+            with pytest.raises(ValueError):
+                launch(**swap)
+                pytest.fail(f"{what} was accepted")
+        for mode in (-1, 2):
+            with pytest.raises(ValueError, match="mode"):
+                launch(mode=mode)
+        with pytest.raises(ValueError):
+            hip_ops.fused_gradients("binary:logistic", good["margin"], good["y"][:10])
+        with pytest.raises(ValueError):
+            hip_ops.fused_gradients("binary:logistic", good["margin"], good["y"], good["w"][:10])
+        torch.cuda.synchronize()
+        assert bool((good["gh"] == -7.0).all())  # nothing was launched
+        launch()  # the same arguments, unbroken, run
+        launch(w=torch.empty(0, **f32))
+        torch.cuda.synchronize()
+        assert bool((good["gh"][:, 0] == 0.5).all())
+
 
 class TestMulticlassPipeline:
     """Pipelined multiclass (per-class slots, one drain) must produce the
