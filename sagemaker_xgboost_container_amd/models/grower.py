@@ -50,6 +50,11 @@ class GrowParams:
         self.min_child_weight = float(p.get("min_child_weight", 1.0))
         self.max_delta_step = float(p.get("max_delta_step", 0.0))
         self.subsample = float(p.get("subsample", 1.0))
+        self.sampling_method = str(p.get("sampling_method") or "uniform")
+        if self.sampling_method not in ("uniform", "gradient_based"):
+            raise ValueError(
+                "sampling_method must be 'uniform' or 'gradient_based', got %r" % self.sampling_method
+            )
         self.colsample_bytree = float(p.get("colsample_bytree", 1.0))
         self.colsample_bylevel = float(p.get("colsample_bylevel", 1.0))
         self.colsample_bynode = float(p.get("colsample_bynode", 1.0))
@@ -136,6 +141,7 @@ class HistGrower:
             and self.p.grow_policy != "lossguide"
         )
         self._fallback_logged = False
+        self._sampling_logged = False
         self.inter_sets = None
         if self.p.interaction_constraints:
             self.inter_sets = [set(group) for group in self.p.interaction_constraints]
@@ -222,6 +228,46 @@ class HistGrower:
         for nid, parent_nid, sibling_nid in derived:
             node_hist[nid] = node_hist[parent_nid] - node_hist[sibling_nid]
 
+    def _sample_rows(self, gh):
+        """This tree's row sample: (rows, gh_for_tree). `rows` is an
+        ascending int32 row list, or None for the full data (level 0 then
+        streams the original matrix).
+
+        uniform keeps each row with probability `subsample`.
+        gradient_based (Minimal Variance Sampling) keeps row i with
+        probability p_i = min(1, r_i / mu), r_i = sqrt(g_i^2 + h_i^2), where
+        sum_i p_i = subsample * n, and multiplies a kept pair by 1 / p_i:
+        gh_for_tree is that rescaled tensor. Both draw one rand(n) from the
+        same generator at the same place. With a communicator every rank
+        thresholds its own shard (no collective).
+        """
+        p = self.p
+        if p.subsample >= 1.0:
+            return None, gh
+        n = self.qm.num_row
+        u = torch.rand(n, device=self.device, generator=self.generator)
+        if p.sampling_method != "gradient_based":
+            return (u < p.subsample).nonzero(as_tuple=True)[0].to(torch.int32), gh
+        if not self._sampling_logged:
+            self._sampling_logged = True
+            logger.info(
+                "sampling_method=gradient_based: each tree samples about %.3g of the rows by "
+                "gradient magnitude%s",
+                p.subsample,
+                " (threshold computed per rank, on its own shard)" if self.comm is not None else "",
+            )
+        return self.backend.gradient_sample(gh, p.subsample, u)
+
+    def _gradient_sampled(self, sample_rows):
+        """Does this tree draw a gradient-based sample? Such a tree's leaf
+        values belong on every training row's margin: the rows it dropped
+        are the well-fitted ones, not a random subset."""
+        return (
+            sample_rows is None
+            and self.p.subsample < 1.0
+            and self.p.sampling_method == "gradient_based"
+        )
+
     def grow(self, gh, sample_rows=None):
         """Grow one tree from (n, 2) float32 gradients.
 
@@ -231,16 +277,13 @@ class HistGrower:
         """
         qm = self.qm
         p = self.p
-        n = qm.num_row
         if sample_rows is not None:
             rows = sample_rows
-        elif p.subsample < 1.0:
-            keep = torch.rand(n, device=self.device, generator=self.generator) < p.subsample
-            rows = keep.nonzero(as_tuple=True)[0].to(torch.int32)
         else:
-            rows = None  # full data: level 0 streams the original matrix
+            rows, gh = self._sample_rows(gh)
 
         self.state = self.backend.make_tree_state(qm, gh, rows)
+        self.state.margin_all_rows = self._gradient_sampled(sample_rows)
         cap = self.state.cap
 
         scale = self.backend.compute_scale(gh, comm=self.comm)
@@ -464,12 +507,9 @@ class HistGrower:
         stream = self._class_stream(slot)
         stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(stream):
-            if p.subsample < 1.0:
-                keep = torch.rand(n, device=self.device, generator=self.generator) < p.subsample
-                rows = keep.nonzero(as_tuple=True)[0].to(torch.int32)
-            else:
-                rows = None
+            rows, gh = self._sample_rows(gh)
             state = self.backend.make_tree_state(qm, gh, rows, slot=slot)
+            state.margin_all_rows = self._gradient_sampled(None)
             self.state = state
             scale = self.backend.compute_scale(gh, comm=None)
             tree_mask = self._sample_features(p.colsample_bytree, None)

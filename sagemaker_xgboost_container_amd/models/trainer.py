@@ -383,6 +383,25 @@ def train(
 
     booster = container.before_training(booster)
 
+    train_tree_margin = [None]  # built on first use: the CSR form uploads a copy
+
+    def add_tree_to_margin(state, tree, leaf_jobs, cls, scale=1.0):
+        """Add a new tree (leaf_jobs already carry `scale`) to the training
+        margin. The tree's own state knows the rows it grew on and updates
+        those; a gradient-sampled tree (`margin_all_rows`) goes to every
+        row — by the state's traversal of the bin matrix where it has one,
+        else by predicting the tree over the training data."""
+        if not getattr(state, "margin_all_rows", False) or getattr(state, "_traverse", None) is not None:
+            state.update_margins(margin[:, cls], leaf_jobs)
+            return
+        if train_tree_margin[0] is None:
+            train_tree_margin[0] = (
+                _csr_tree_margin_fn(Xcsr, device) if sparse_mode
+                else (lambda t: backend.predict_tree(t, X))
+            )
+        contrib = train_tree_margin[0](tree)
+        margin[:, cls] += contrib * scale if scale != 1.0 else contrib
+
     for epoch in range(start_round, start_round + num_boost_round):
         if container.before_iteration(booster, epoch):
             break
@@ -457,7 +476,7 @@ def train(
                     ]
                     for cls, handle in enumerate(handles):
                         tree, leaf_jobs = grower.grow_finish(handle)
-                        grower.state.update_margins(margin[:, cls], leaf_jobs)
+                        add_tree_to_margin(grower.state, tree, leaf_jobs, cls)
                         round_trees.append(tree)
                         round_info.append(cls)
                         for es in eval_sets:
@@ -469,7 +488,7 @@ def train(
                     tree, leaf_jobs = grower.grow(gh_cls)
                     if new_tree_scale != 1.0:
                         leaf_jobs = [(p_, s_, e_, v_ * new_tree_scale) for p_, s_, e_, v_ in leaf_jobs]
-                    grower.state.update_margins(margin[:, cls], leaf_jobs)
+                    add_tree_to_margin(grower.state, tree, leaf_jobs, cls, new_tree_scale)
                     round_trees.append(tree)
                     round_info.append(cls)
                     for es in eval_sets:

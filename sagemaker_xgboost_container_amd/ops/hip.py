@@ -91,6 +91,40 @@ def fused_gradients(name, margin, y, weight=None, scale_pos_weight=1.0):
     return gh
 
 
+# int64 words of the sampler's scratch: 4 radix passes x 256 buckets x
+# (count, significand sum), then 4 words of select state
+_MVS_WORK_WORDS = 4 * 256 * 2 + 4
+_MVS_APPLY_GRID = 2048
+
+
+def mvs_threshold(gh, S):
+    """Threshold mu of gradient-based sampling for (n, 2) float32 gradients
+    and a real sample size S, as a float32 [1] device tensor (no readback):
+    the radix select of csrc/smxgb_sampling.hip, bit-deterministic."""
+    gh = gh.to(torch.float32).contiguous()
+    work = torch.zeros(_MVS_WORK_WORDS, dtype=torch.int64, device=gh.device)
+    mu = torch.empty(1, dtype=torch.float32, device=gh.device)
+    _K.mvs_threshold(gh, float(S), work, mu)
+    return mu
+
+
+def gradient_sample(gh, subsample, u):
+    """Gradient-based row sample (see torch_ref.gradient_sample) on the
+    device. The rescaled tensor carries its own `_smxgb_absmax`; the
+    unscaled tensor's absmax and root sum do not apply to it."""
+    gh = gh.to(torch.float32).contiguous()
+    n = gh.shape[0]
+    mu = mvs_threshold(gh, float(subsample) * n)
+    out = torch.empty_like(gh)
+    keep = torch.empty(n, dtype=torch.uint8, device=gh.device)
+    blocks = max(1, min((n + 255) // 256, _MVS_APPLY_GRID))
+    pmax = torch.empty((blocks, 2), dtype=torch.float32, device=gh.device)
+    _K.mvs_apply(gh, u.to(torch.float32).contiguous(), mu, out, keep, pmax)
+    out._smxgb_absmax = pmax.amax(dim=0).contiguous()
+    rows = keep.nonzero(as_tuple=True)[0].to(torch.int32)
+    return rows, out
+
+
 def _padded_words(pairs):
     """LDS u64 words for `pairs` histogram slots incl. bank-skew padding."""
     return (pairs + (pairs >> 3) + 1) * 2
@@ -836,16 +870,20 @@ class TreeState:
         # (split heap, depth, leaf heap indices) of a device-grown tree whose
         # margins are updated by traversal; None selects the leaf scatter
         self._traverse = None
+        # set by the grower for a gradient-sampled tree: its leaf values go
+        # to every training row's margin, not only to the sampled rows'
+        self.margin_all_rows = False
 
     def traverse_ok(self):
         """Margins of this tree can be updated by streaming the original
-        bin matrix through the finished tree: full-data state only (a
-        subsampled tree must leave the rows it did not see untouched).
+        bin matrix through the finished tree: a full-data state, or a
+        gradient-sampled one (`margin_all_rows`). A uniformly subsampled
+        tree must leave the rows it did not see untouched.
         SMXGB_LEAF_UPDATE=scatter keeps the row-id scatter for A/B runs."""
         mode = _os.environ.get("SMXGB_LEAF_UPDATE", "traverse")
         if mode not in ("traverse", "scatter"):
             raise ValueError(f"SMXGB_LEAF_UPDATE must be 'traverse' or 'scatter', got {mode!r}")
-        return mode == "traverse" and self._bins_init is self.qm.bins
+        return mode == "traverse" and (self._bins_init is self.qm.bins or self.margin_all_rows)
 
     def _src(self, parity):
         if parity == 0 and self._level0:

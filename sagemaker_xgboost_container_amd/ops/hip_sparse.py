@@ -50,6 +50,9 @@ MIRRORS_DEVICE_GROWER = True
 compute_scale = hip.compute_scale
 hist_to_float = hip.hist_to_float
 find_splits = hip.find_splits
+# gradient-based row sampling reads the dense (n, 2) gradients only
+mvs_threshold = hip.mvs_threshold
+gradient_sample = hip.gradient_sample
 
 # rows of a segment per block. A row costs its stored entries (tens for the
 # wide data this path is for, against f for a dense row), so blocks take

@@ -34,6 +34,9 @@ NAME = "sparse_ref"
 compute_scale = torch_ref.compute_scale
 hist_to_float = torch_ref.hist_to_float
 find_splits = torch_ref.find_splits
+# gradient-based row sampling reads the dense (n, 2) gradients only
+mvs_threshold = torch_ref.mvs_threshold
+gradient_sample = torch_ref.gradient_sample
 
 
 class SparseQuantizedMatrix:

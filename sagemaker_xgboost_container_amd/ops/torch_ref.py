@@ -13,7 +13,11 @@ Interface (segment-based, one device sync per tree level):
   partition_level(qm, src, dst, segs, feats, bins, dls) -> left counts (host)
   update_margins(margin_col, bufs, leaf_jobs)
   predict_tree(tree, X)                 -> (n,) margin contribution
+  gradient_sample(gh, subsample, u)     -> (rows, rescaled gh) of
+                                           sampling_method=gradient_based
 """
+import math
+
 import torch
 
 NAME = "torch_ref"
@@ -203,6 +207,58 @@ def update_margins(margin_col, bufs, leaf_jobs):
     for parity, start, end, value in leaf_jobs:
         rows = bufs[parity][start:end].long()
         margin_col[rows] += value
+
+
+def _mvs_norm(gh):
+    g = gh[:, 0].to(torch.float32)
+    h = gh[:, 1].to(torch.float32)
+    return torch.sqrt(g * g + h * h)
+
+
+def mvs_threshold(gh, S):
+    """Threshold mu of gradient-based sampling (Minimal Variance Sampling)
+    as a float32 scalar tensor on gh's device: the solution of
+    sum_i min(1, r_i / mu) = S with r_i = sqrt(g_i^2 + h_i^2), or 0 when no
+    more than S rows have r_i > 0 (all of them are then kept).
+
+    Reference form: sort, float64 cumulative sum, closed form. With the k
+    largest rows certain (p = 1), mu_k = sum(rest) / (S - k); the solution
+    is the smallest k whose largest uncertain row is <= mu_k.
+    """
+    S = float(S)
+    r = _mvs_norm(gh).to(torch.float64)
+    r = torch.sort(r[r > 0]).values
+    m = r.numel()
+    if m <= S:
+        return torch.zeros((), dtype=torch.float32, device=gh.device)
+    csum = torch.cumsum(r, 0)
+    # k < S keeps the denominator positive; m > S leaves a row uncertain
+    k = torch.arange(0, min(m, math.ceil(S)), device=gh.device)
+    top = m - 1 - k  # largest uncertain row when k rows are certain
+    mu_k = csum[top] / (S - k.to(torch.float64))
+    first = int((r[top] <= mu_k).nonzero()[0])
+    return mu_k[first].to(torch.float32)
+
+
+def gradient_sample(gh, subsample, u):
+    """Gradient-based row sample of one tree's (n, 2) float32 gradients.
+
+    Row i is kept when u_i < p_i = min(1, r_i / mu) (mu = 0: p_i = 1 where
+    r_i > 0) and its pair is multiplied by 1 / p_i; dropped rows get a zero
+    pair. Returns (ascending int32 row list, rescaled (n, 2) tensor)."""
+    n = gh.shape[0]
+    mu = mvs_threshold(gh, float(subsample) * n)
+    r = _mvs_norm(gh)
+    if float(mu) > 0.0:
+        p = torch.clamp(r / mu, max=1.0)
+    else:
+        p = (r > 0).to(torch.float32)
+    keep = u < p
+    inv = torch.where(keep, 1.0 / p, torch.zeros_like(p))
+    out = gh.to(torch.float32) * inv.unsqueeze(1)
+    out = torch.where(keep.unsqueeze(1), out, torch.zeros_like(out))
+    rows = keep.nonzero(as_tuple=True)[0].to(torch.int32)
+    return rows, out
 
 
 def predict_tree(tree, X):
