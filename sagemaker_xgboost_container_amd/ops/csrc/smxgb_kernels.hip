@@ -999,103 +999,6 @@ __global__ __launch_bounds__(HIST_BLOCK) void derive_level_kernel(
   }
 }
 
-// LDS-staged partition variant: each tile's payload (bins rows, gh, row
-// ids) is read from HBM exactly ONCE into LDS during classification, and
-// the scatter writes read LDS instead of re-pulling the source through L2
-// — removes the second source pass (~28 B/row/level on Higgs shape).
-// u8 bins with nfeat % 4 == 0 only; dynamic LDS = tile*(8 + nd*4 + 8) B.
-template <int TILE>
-__global__ __launch_bounds__(HIST_BLOCK) void partition_device_lds_kernel(
-    const unsigned char* __restrict__ src_bins, const float2* __restrict__ src_gh,
-    const int* __restrict__ src_rows, unsigned char* __restrict__ dst_bins,
-    float2* __restrict__ dst_gh, int* __restrict__ dst_rows,
-    const LevelNode* __restrict__ nodes, const int* __restrict__ part_prefix,
-    const LevelWork* __restrict__ work, const float* __restrict__ split_packed,
-    int* __restrict__ counters, int k, int nfeat, int missing_bin,
-    int copy_payload) {
-  extern __shared__ unsigned char smem[];
-  const int nd = nfeat >> 2;
-  float2* lgh = reinterpret_cast<float2*>(smem);                       // [TILE]
-  uchar4* lbins = reinterpret_cast<uchar4*>(smem + TILE * 8);          // [TILE*nd]
-  int* lrows = reinterpret_cast<int*>(smem + TILE * 8 + (size_t)TILE * nd * 4);
-  int* ldest = lrows + TILE;
-  __shared__ int lcnt, rcnt, lbase, rbase;
-  const int total = work->part_total;
-
-  for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
-    const int slot = find_slot(part_prefix, k, vb);
-    const LevelNode node = nodes[slot];
-    const float* sp6 = split_packed + slot * 6;
-    if (sp6[0] <= 0.0f || node.end <= node.start) continue;
-    const int feature = (int)sp6[1];
-    const int split_bin = (int)sp6[2];
-    const int default_left = sp6[3] > 0.5f ? 1 : 0;
-    const int chunk = vb - part_prefix[slot];
-    const int nb = part_prefix[slot + 1] - part_prefix[slot];
-    const long long tile_step = (long long)nb * TILE;
-
-    for (long long tile = node.start + (long long)chunk * TILE; tile < node.end;
-         tile += tile_step) {
-      if (threadIdx.x == 0) {
-        lcnt = 0;
-        rcnt = 0;
-      }
-      __syncthreads();
-      const int tile_n = (int)min((long long)TILE, node.end - tile);
-      // single coalesced source pass: bins -> LDS (vec4), gh + rows -> LDS
-      const uchar4* sb4 = reinterpret_cast<const uchar4*>(src_bins);
-      for (int u = threadIdx.x; u < tile_n * nd; u += blockDim.x) {
-        lbins[u] = sb4[(tile + (u / nd)) * (long long)nd + (u % nd)];
-      }
-      for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
-        lgh[i] = src_gh[tile + i];
-        lrows[i] = src_rows[tile + i];
-      }
-      __syncthreads();
-      for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
-        const int b =
-            (int)reinterpret_cast<const unsigned char*>(lbins)[i * (long long)nfeat + feature];
-        const bool left = (b == missing_bin) ? (default_left != 0) : (b <= split_bin);
-        ldest[i] = left ? atomicAdd(&lcnt, 1) : ~atomicAdd(&rcnt, 1);
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        lbase = atomicAdd(&counters[slot * 2], lcnt);
-        rbase = atomicAdd(&counters[slot * 2 + 1], rcnt);
-      }
-      __syncthreads();
-      if (copy_payload) {
-        int log2p = 0;
-        while ((1 << log2p) < nd) ++log2p;
-        const int mask = (1 << log2p) - 1;
-        uchar4* db4 = reinterpret_cast<uchar4*>(dst_bins);
-        for (int u = threadIdx.x; u < (tile_n << log2p); u += blockDim.x) {
-          const int i = u >> log2p;
-          const int f4 = u & mask;
-          if (f4 >= nd) continue;
-          const int d = ldest[i];
-          const long long dst =
-              d >= 0 ? (long long)node.start + lbase + d : (long long)node.end - 1 - rbase - (~d);
-          db4[dst * nd + f4] = lbins[i * nd + f4];
-        }
-        for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
-          const int d = ldest[i];
-          const long long dst =
-              d >= 0 ? (long long)node.start + lbase + d : (long long)node.end - 1 - rbase - (~d);
-          dst_gh[dst] = lgh[i];
-        }
-      }
-      for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
-        const int d = ldest[i];
-        const long long dst =
-            d >= 0 ? (long long)node.start + lbase + d : (long long)node.end - 1 - rbase - (~d);
-        dst_rows[dst] = lrows[i];
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // partition driven by the device job table (virtual blocks)
 template <typename BinT>
 __global__ __launch_bounds__(HIST_BLOCK) void partition_device_kernel(
@@ -1196,6 +1099,158 @@ __global__ __launch_bounds__(HIST_BLOCK) void partition_device_kernel(
         }
       }
       __syncthreads();
+    }
+  }
+}
+
+// Single-read partition: every tile's payload is loaded ONCE into registers,
+// classified from the register that holds the split feature's byte, and
+// stored from those registers after the tile's two global atomics. The
+// classic kernel re-reads the whole tile for the copy; at the flagship shape
+// ~15 MB of tiles are live per XCD between the two reads (3.5x its L2), so
+// the second read goes to memory again.
+//
+// Lane mapping: 8 lanes per row, lane `sub` holds dword `sub` of the row
+// (nd = nfeat/4 <= 8; lanes sub >= nd idle, as in the classic copy loop), a
+// pass covers BLOCK/8 rows and a lane holds R passes: TILE = R * BLOCK / 8.
+// gh (and the row id with ROWS) of tile row g*BLOCK + tid sit in lane tid.
+// Source addresses are a block-uniform tile base plus one 32-bit lane
+// offset; the passes differ by a uniform step, so no per-load address lives
+// in VGPRs. u8 bins, nfeat % 4 == 0, nfeat <= 32, payload always copied.
+template <int BLOCK, int R, bool ROWS, bool FULL>
+__device__ __forceinline__ void partition_staged_tile(
+    const unsigned* __restrict__ sb, const float2* __restrict__ sgh,
+    const int* __restrict__ srows, unsigned* __restrict__ db, float2* __restrict__ dgh,
+    int* __restrict__ drows, int* ldest, int* lcnt, int* rcnt, int* lbase, int* rbase,
+    int* __restrict__ counter, long long left0, long long right0, int tile_n, int nd,
+    int fdw, int fsh, int split_bin, int missing_bin, bool default_left) {
+  constexpr int RPP = BLOCK / 8;
+  constexpr int G = R / 8;
+  const int sub = threadIdx.x & 7;
+  const int rlane = threadIdx.x >> 3;
+  const unsigned lane_off = (unsigned)(rlane * nd + sub);
+  const int pass_step = RPP * nd;
+  unsigned v[R];
+  float2 gh[G];
+  int rid[G];
+  // 1. the whole tile, loads issued back to back
+  // (a tail tile leaves the registers of rows past its end at zero)
+  if (sub < nd) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      v[j] = 0u;
+      if (FULL || j * RPP + rlane < tile_n) v[j] = (sb + (long long)j * pass_step)[lane_off];
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int i = g * BLOCK + (int)threadIdx.x;
+    gh[g] = make_float2(0.f, 0.f);
+    rid[g] = 0;
+    if (FULL || i < tile_n) {
+      gh[g] = sgh[i];
+      if (ROWS) rid[g] = srows[i];
+    }
+  }
+  // 2. classify from the register holding the split feature's byte
+  if (sub == fdw) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = j * RPP + rlane;
+      if (FULL || i < tile_n) {
+        const int b = (int)((v[j] >> fsh) & 0xffu);
+        const bool left = (b == missing_bin) ? default_left : (b <= split_bin);
+        ldest[i] = left ? atomicAdd(lcnt, 1) : ~atomicAdd(rcnt, 1);
+      }
+    }
+  }
+  __syncthreads();
+  // 3. one returning global atomic per side; the LDS counters are zeroed
+  // for the next tile here (nothing touches them before the closing barrier)
+  if (threadIdx.x == 0) {
+    *lbase = atomicAdd(&counter[0], *lcnt);
+    *rbase = atomicAdd(&counter[1], *rcnt);
+    *lcnt = 0;
+    *rcnt = 0;
+  }
+  __syncthreads();
+  // 4. store the registers; destinations are computed just before each store
+  const long long lb = left0 + *lbase;
+  const long long rb = right0 - *rbase;
+  if (sub < nd) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = j * RPP + rlane;
+      if (FULL || i < tile_n) {
+        const int d = ldest[i];
+        const long long dst = d >= 0 ? lb + d : rb - (~d);
+        db[dst * nd + sub] = v[j];
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int i = g * BLOCK + (int)threadIdx.x;
+    if (FULL || i < tile_n) {
+      const int d = ldest[i];
+      const long long dst = d >= 0 ? lb + d : rb - (~d);
+      dgh[dst] = gh[g];
+      if (ROWS) drows[dst] = rid[g];
+    }
+  }
+  __syncthreads();
+}
+
+template <int BLOCK, int R, bool ROWS>
+__global__ __launch_bounds__(BLOCK) void partition_device_staged_kernel(
+    const unsigned char* __restrict__ src_bins, const float2* __restrict__ src_gh,
+    const int* __restrict__ src_rows, unsigned char* __restrict__ dst_bins,
+    float2* __restrict__ dst_gh, int* __restrict__ dst_rows,
+    const LevelNode* __restrict__ nodes, const int* __restrict__ part_prefix,
+    const LevelWork* __restrict__ work, const float* __restrict__ split_packed,
+    int* __restrict__ counters, int k, int nfeat, int missing_bin) {
+  constexpr int TILE = R * BLOCK / 8;
+  __shared__ int ldest[TILE];
+  __shared__ int lcnt, rcnt, lbase, rbase;
+  const int total = work->part_total;
+  const int nd = nfeat >> 2;
+  if (threadIdx.x == 0) {
+    lcnt = 0;
+    rcnt = 0;
+  }
+  __syncthreads();
+
+  for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
+    const int slot = find_slot(part_prefix, k, vb);
+    const LevelNode node = nodes[slot];
+    const float* sp6 = split_packed + slot * 6;
+    if (sp6[0] <= 0.0f || node.end <= node.start) continue;
+    const int feature = (int)sp6[1];
+    const int split_bin = (int)sp6[2];
+    const bool default_left = sp6[3] > 0.5f;
+    const int fdw = feature >> 2;
+    const int fsh = (feature & 3) * 8;
+    const int chunk = vb - part_prefix[slot];
+    const int nb = part_prefix[slot + 1] - part_prefix[slot];
+    const long long tile_step = (long long)nb * TILE;
+    unsigned* db = reinterpret_cast<unsigned*>(dst_bins);
+
+    for (long long tile = node.start + (long long)chunk * TILE; tile < node.end;
+         tile += tile_step) {
+      // tile < node.end, so both fit an int
+      const int tile_n = min(TILE, node.end - (int)tile);
+      const unsigned* sb = reinterpret_cast<const unsigned*>(src_bins) + tile * nd;
+      if (tile_n == TILE) {
+        partition_staged_tile<BLOCK, R, ROWS, true>(
+            sb, src_gh + tile, src_rows + tile, db, dst_gh, dst_rows, ldest, &lcnt, &rcnt,
+            &lbase, &rbase, counters + slot * 2, node.start, (long long)node.end - 1, tile_n,
+            nd, fdw, fsh, split_bin, missing_bin, default_left);
+      } else {
+        partition_staged_tile<BLOCK, R, ROWS, false>(
+            sb, src_gh + tile, src_rows + tile, db, dst_gh, dst_rows, ldest, &lcnt, &rcnt,
+            &lbase, &rbase, counters + slot * 2, node.start, (long long)node.end - 1, tile_n,
+            nd, fdw, fsh, split_bin, missing_bin, default_left);
+      }
     }
   }
 }
@@ -2224,41 +2279,69 @@ void grow_derive_level(torch::Tensor level_hist, torch::Tensor parent_hist, torc
                      (int)k, slots2);
 }
 
-// SMXGB_PART_LDS: 0 = classic two-pass partition, 1024/2048 (or "1" ->
-// 1024) = LDS-staged single-source-pass variant (A/B experiment).
-static int part_lds_mode() {
-  static int mode = [] {
-    const char* e = getenv("SMXGB_PART_LDS");
-    if (e == nullptr) return 0;
-    const int v = atoi(e);
-    return v == 1 ? 1024 : v;
-  }();
-  return mode;
+// Which kernel partitions a level (SMXGB_PARTITION, pushed in by ops/hip.py
+// through set_partition_mode):
+//   0                 the classic two-read kernel everywhere
+//   1                 the staged single-read kernel where it applies
+//   512 / 1024 / 2048 the staged kernel at that tile (A/B sweeps; 1 = 2048)
+static int g_partition_mode = 1;
+
+void set_partition_mode(int64_t mode) {
+  TORCH_CHECK_VALUE(mode == 0 || mode == 1 || mode == 512 || mode == 1024 || mode == 2048,
+                    "partition mode must be 0, 1, 512, 1024 or 2048, got ", mode);
+  g_partition_mode = (int)mode;
 }
 
-static bool launch_part_lds(int grid, hipStream_t stream, const unsigned char* src_bins,
-                            const float2* src_gh, const int* src_rows,
-                            unsigned char* dst_bins, float2* dst_gh, int* dst_rows,
-                            const LevelNode* nodes, const int* part_prefix,
-                            const LevelWork* work, const float* split_packed, int* counters,
-                            int k, int nfeat, int missing_bin, int copy_payload,
-                            int copy_rows) {
-  const int tile = part_lds_mode();
-  // the staged variant always moves row ids: not selected without them
-  if (tile == 0 || (nfeat & 3) != 0 || !copy_rows) return false;
-  const size_t lds = (size_t)tile * (8 + (size_t)(nfeat >> 2) * 4 + 8);
-  if (lds > 158 * 1024) return false;
+// Rows per tile of the staged kernel, 0 where the classic kernel runs
+// (int16 bins, widths the 8-lane row group does not cover, the payload-free
+// last-level form). Measured at 12.5M x 28 (profiles/
+// r11_partition_single_read.md): 580 / 318 / 190 us per launch at 512 / 1024 /
+// 2048 rows per tile, at every level alike, so the barrier and atomic round
+// trip that each tile pays sets the time, not the node's two counter words
+// (rows / 2048 returning atomics per word at k = 1: 69 us of 190). Every
+// level takes the 2048-row tile on a 512-thread block.
+static int staged_partition_tile(int nfeat, bool u8, int copy_payload) {
+  if (g_partition_mode == 0 || !u8 || !copy_payload || nfeat < 4 || nfeat > 32 ||
+      (nfeat & 3) != 0)
+    return 0;
+  return g_partition_mode == 1 ? 2048 : g_partition_mode;
+}
+
+int64_t partition_tile(int64_t nfeat, int64_t u8, int64_t copy_payload) {
+  return staged_partition_tile((int)nfeat, u8 != 0, (int)copy_payload);
+}
+
+static bool launch_part_staged(int grid, hipStream_t stream, const unsigned char* src_bins,
+                               const float2* src_gh, const int* src_rows,
+                               unsigned char* dst_bins, float2* dst_gh, int* dst_rows,
+                               const LevelNode* nodes, const int* part_prefix,
+                               const LevelWork* work, const float* split_packed, int* counters,
+                               int k, int nfeat, int missing_bin, int copy_payload,
+                               int copy_rows) {
+  const int tile = staged_partition_tile(nfeat, true, copy_payload);
+  if (tile == 0) return false;
+#define SMXGB_LAUNCH_STAGED(BLOCK, R)                                                          \
+  do {                                                                                         \
+    if (copy_rows) {                                                                           \
+      hipLaunchKernelGGL((partition_device_staged_kernel<BLOCK, R, true>), dim3(grid),         \
+                         dim3(BLOCK), 0, stream, src_bins, src_gh, src_rows, dst_bins, dst_gh, \
+                         dst_rows, nodes, part_prefix, work, split_packed, counters, k, nfeat, \
+                         missing_bin);                                                         \
+    } else {                                                                                   \
+      hipLaunchKernelGGL((partition_device_staged_kernel<BLOCK, R, false>), dim3(grid),        \
+                         dim3(BLOCK), 0, stream, src_bins, src_gh, src_rows, dst_bins, dst_gh, \
+                         dst_rows, nodes, part_prefix, work, split_packed, counters, k, nfeat, \
+                         missing_bin);                                                         \
+    }                                                                                          \
+  } while (0)
   if (tile == 2048) {
-    hipLaunchKernelGGL(partition_device_lds_kernel<2048>, dim3(grid), dim3(HIST_BLOCK), lds,
-                       stream, src_bins, src_gh, src_rows, dst_bins, dst_gh, dst_rows, nodes,
-                       part_prefix, work, split_packed, counters, k, nfeat, missing_bin,
-                       copy_payload);
+    SMXGB_LAUNCH_STAGED(512, 32);
+  } else if (tile == 1024) {
+    SMXGB_LAUNCH_STAGED(256, 32);
   } else {
-    hipLaunchKernelGGL(partition_device_lds_kernel<1024>, dim3(grid), dim3(HIST_BLOCK), lds,
-                       stream, src_bins, src_gh, src_rows, dst_bins, dst_gh, dst_rows, nodes,
-                       part_prefix, work, split_packed, counters, k, nfeat, missing_bin,
-                       copy_payload);
+    SMXGB_LAUNCH_STAGED(256, 16);
   }
+#undef SMXGB_LAUNCH_STAGED
   return true;
 }
 
@@ -2270,13 +2353,13 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
                           int64_t copy_payload, int64_t copy_rows) {
   auto stream = current_stream();
   if (src_bins.scalar_type() == torch::kUInt8) {
-    if (launch_part_lds((int)grid, stream, src_bins.data_ptr<unsigned char>(),
-                        (const float2*)src_gh.data_ptr<float>(), src_rows.data_ptr<int>(),
-                        dst_bins.data_ptr<unsigned char>(), (float2*)dst_gh.data_ptr<float>(),
-                        dst_rows.data_ptr<int>(), (const LevelNode*)nodes.data_ptr<int>(),
-                        part_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
-                        split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)k,
-                        (int)nfeat, (int)missing_bin, (int)copy_payload, (int)copy_rows))
+    if (launch_part_staged((int)grid, stream, src_bins.data_ptr<unsigned char>(),
+                           (const float2*)src_gh.data_ptr<float>(), src_rows.data_ptr<int>(),
+                           dst_bins.data_ptr<unsigned char>(), (float2*)dst_gh.data_ptr<float>(),
+                           dst_rows.data_ptr<int>(), (const LevelNode*)nodes.data_ptr<int>(),
+                           part_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
+                           split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)k,
+                           (int)nfeat, (int)missing_bin, (int)copy_payload, (int)copy_rows))
       return;
     hipLaunchKernelGGL(partition_device_kernel<unsigned char>, dim3((int)grid), dim3(HIST_BLOCK),
                        0, stream, src_bins.data_ptr<unsigned char>(),
@@ -2475,10 +2558,10 @@ void grow_tree_enqueue(
     // ... and with the filtered deepest histogram, neither is level D-2
     if (filter_last && d == (int)D - 2) continue;
     if (u8) {
-      if (!launch_part_lds((int)part_grid, stream, (const unsigned char*)src_bins, src_gh,
-                           src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d, pp_d,
-                           work_d, splits_d, counts_d, k, (int)nfeat, (int)missing_bin,
-                           copy_payload, copy_rows))
+      if (!launch_part_staged((int)part_grid, stream, (const unsigned char*)src_bins, src_gh,
+                              src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d,
+                              pp_d, work_d, splits_d, counts_d, k, (int)nfeat,
+                              (int)missing_bin, copy_payload, copy_rows))
         hipLaunchKernelGGL(partition_device_kernel<unsigned char>, dim3((int)part_grid),
                            dim3(HIST_BLOCK), 0, stream, (const unsigned char*)src_bins, src_gh,
                            src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d, pp_d,
@@ -2566,6 +2649,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_convert_level", &grow_convert_level);
   m.def("grow_derive_level", &grow_derive_level);
   m.def("grow_partition_level", &grow_partition_level);
+  m.def("set_partition_mode", &set_partition_mode,
+        "0 classic, 1 staged, 512/1024/2048 staged at that tile");
+  m.def("partition_tile", &partition_tile,
+        "rows per tile of the staged partition for (nfeat, u8, copy_payload); 0 = classic");
   m.def("grow_node_mask", &grow_node_mask, "interaction-constraint bitsets + node mask of a level");
   m.def("grow_tree_enqueue", &grow_tree_enqueue, "whole depthwise tree enqueued from one call");
   m.def("partition_compact", &partition_compact, "compacting partition (rows+bins+gh rewrite)");

@@ -1047,6 +1047,35 @@ if _DEEPEST_HIST not in _DEEPEST_HIST_MODES:
     raise ValueError(
         f"SMXGB_DEEPEST_HIST must be one of {sorted(_DEEPEST_HIST_MODES)}, got {_DEEPEST_HIST!r}"
     )
+# Which kernel partitions a level's rows: "staged" reads every source row
+# once (the tile is held in registers between classification and the copy)
+# wherever it applies: u8 bins, a width that is a multiple of 4 up to 32, and
+# the payload is copied; everything else runs the classic kernel. "classic"
+# keeps the two-read kernel everywhere for A/B runs; "staged-512",
+# "staged-1024" and "staged-2048" pick the rows per tile ("staged" is the
+# 2048-row geometry, the fastest measured). Read once at import like
+# SMXGB_DEEPEST_HIST; set_partition_mode() switches it within a process.
+_PARTITION = _os.environ.get("SMXGB_PARTITION", "staged")
+_PARTITION_MODES = {
+    "classic": 0, "staged": 1, "staged-512": 512, "staged-1024": 1024, "staged-2048": 2048,
+}
+
+
+def set_partition_mode(mode):
+    """Select the partition kernel ("classic", "staged", "staged-<tile>") for
+    every tree grown from now on; returns the mode that was set before."""
+    global _PARTITION
+    if mode not in _PARTITION_MODES:
+        raise ValueError(
+            f"SMXGB_PARTITION must be one of {sorted(_PARTITION_MODES)}, got {mode!r}"
+        )
+    previous = _PARTITION
+    _K.set_partition_mode(_PARTITION_MODES[mode])
+    _PARTITION = mode
+    return previous
+
+
+set_partition_mode(_PARTITION)
 
 
 def interaction_union_bitsets(interaction_sets, f):
@@ -1238,7 +1267,7 @@ class DeviceGrower:
             # captured body must be allocation-free — see _enqueue_body)
             if rootsum is None:
                 rootsum = st._gh_init.to(torch.float64).sum(0)
-            key = (st.cap, split_params, self.traverse, _DEEPEST_HIST)
+            key = (st.cap, split_params, self.traverse, _DEEPEST_HIST, _PARTITION)
             dbg = _os.environ.get("SMXGB_GRAPH_DEBUG") == "1"
 
             def _d(msg):
