@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .objectives import create_objective
+from .objectives import create_objective, parse_quantile_alpha
 from .tree import Tree
 
 MODEL_VERSION = [3, 0, 5]  # schema-compatible xgboost version
@@ -42,6 +42,8 @@ def objective_params_from_json(obj_json, params):
         "poisson_regression_param": (("max_delta_step", float),),
         "tweedie_regression_param": (("tweedie_variance_power", float),),
         "pseudo_huber_param": (("huber_slope", float),),
+        # a JSON-array string ("[0.1, 0.9]"); a bare number is accepted too
+        "quantile_loss_param": (("quantile_alpha", parse_quantile_alpha),),
         "aft_loss_param": (
             ("aft_loss_distribution", str),
             ("aft_loss_distribution_scale", float),
@@ -100,6 +102,9 @@ class Booster:
 
     @property
     def n_outputs(self):
+        if self.objective_name == "reg:quantileerror":
+            # one output (and one tree per round) per quantile_alpha
+            return len(parse_quantile_alpha(self.params.get("quantile_alpha", 0.5)))
         return max(1, self.num_class)
 
     @property
@@ -890,6 +895,9 @@ class Booster:
             }
         elif name == "reg:pseudohubererror":
             obj["pseudo_huber_param"] = {"huber_slope": str(p.get("huber_slope", 1.0))}
+        elif name == "reg:quantileerror":
+            alphas = parse_quantile_alpha(p.get("quantile_alpha", 0.5))
+            obj["quantile_loss_param"] = {"quantile_alpha": json.dumps(alphas)}
         elif name == "survival:aft":
             obj["aft_loss_param"] = {
                 "aft_loss_distribution": str(p.get("aft_loss_distribution", "normal")),
@@ -943,7 +951,10 @@ class Booster:
                     "boost_from_average": "1",
                     "num_class": str(self.num_class),
                     "num_feature": str(self.num_features),
-                    "num_target": "1",
+                    # upstream counts the quantiles of reg:quantileerror as targets
+                    "num_target": str(
+                        self.n_outputs if self.objective_name == "reg:quantileerror" else 1
+                    ),
                 },
                 "objective": self._objective_json(),
             },

@@ -30,6 +30,19 @@ def mae(pred, y, weight=None):
     return float((w * (pred - y).abs()).sum() / w.sum())
 
 
+def quantile_loss(pred, y, alphas, weight=None):
+    """Mean pinball loss over rows and alphas: alpha * max(y - p, 0) +
+    (1 - alpha) * max(p - y, 0), column j of pred against alphas[j]. A
+    weighted mean over rows, so a ratio of sums for the distributed
+    aggregation."""
+    p = pred.reshape(y.shape[0], -1).to(torch.float64)
+    a = torch.tensor(list(alphas), dtype=torch.float64, device=p.device)
+    d = y.to(torch.float64).reshape(-1, 1) - p
+    loss = (a * torch.clamp(d, min=0) + (1.0 - a) * torch.clamp(-d, min=0)).mean(dim=1)
+    w = _w(weight, loss)
+    return float((w * loss).sum() / w.sum())
+
+
 def mape(pred, y, weight=None):
     w = _w(weight, y)
     return float((w * ((pred - y) / torch.clamp(y.abs(), min=1e-16)).abs()).sum() / w.sum())
@@ -278,6 +291,15 @@ def evaluate(metric_name, margin, y, weight, objective):
         return mse(pred, y, weight)
     if name == "mae":
         return mae(pred, y, weight)
+    if name == "quantile":
+        alphas = getattr(objective, "alphas", None)
+        if alphas is None:
+            from .objectives import parse_quantile_alpha
+
+            alphas = parse_quantile_alpha(objective.params.get("quantile_alpha", 0.5))
+        if pred.reshape(y.shape[0], -1).shape[1] != len(alphas):
+            raise ValueError("the quantile metric needs one prediction column per quantile_alpha")
+        return quantile_loss(pred, y, alphas, weight)
     if name == "mape":
         return mape(pred, y, weight)
     if name == "rmsle":

@@ -284,6 +284,7 @@ class HistGrower:
 
         self.state = self.backend.make_tree_state(qm, gh, rows)
         self.state.margin_all_rows = self._gradient_sampled(sample_rows)
+        self.tree_rows = rows  # the rows this tree grows on (None: all)
         cap = self.state.cap
 
         scale = self.backend.compute_scale(gh, comm=self.comm)
@@ -519,7 +520,8 @@ class HistGrower:
             if tree_mask is not None:
                 dg.mask = tree_mask.to(torch.uint8).contiguous()
             ev = dg.grow_enqueue(scale, (p.reg_lambda, p.reg_alpha, p.gamma, p.min_child_weight))
-        return {"dg": dg, "ev": ev, "state": state, "cap": state.cap, "stream": stream}
+        return {"dg": dg, "ev": ev, "state": state, "cap": state.cap, "stream": stream,
+                "rows": rows}
 
     def grow_finish(self, handle):
         """Wait for a grow_async tree and build its host Tree."""
@@ -527,6 +529,7 @@ class HistGrower:
         state = handle["state"]
         state._level0 = not bool(splits_np[0, 0] > 0)
         self.state = state  # so the caller's update_margins hits this slot
+        self.tree_rows = handle["rows"]
         tree, leaf_jobs = self._build_tree_from_heap(
             splits_np, counts_np, root_np, handle["cap"]
         )
@@ -553,6 +556,7 @@ class HistGrower:
         # below are placeholders nobody reads; the heap indices are what
         # that update uses.
         leaf_heap = []
+        leaf_nodes = []  # tree node id of each leaf_jobs entry
         from collections import deque
 
         # this loop sits between one tree's readback and the next tree's
@@ -596,7 +600,9 @@ class HistGrower:
                 parity = 0 if d == 0 else d % 2
                 leaf_jobs.append((parity, start, end, float(tree.value[nid])))
                 leaf_heap.append(hidx)
+                leaf_nodes.append(nid)
         self._leaf_heap = leaf_heap
+        self.leaf_nodes = leaf_nodes
         # levels 0..D-1 that held a node: BFS pops the deepest node last
         self._live_levels = min(d + 1, D)
         return tree, leaf_jobs
@@ -731,6 +737,7 @@ class HistGrower:
             depth += 1
 
         finished.extend(frontier)
+        self.leaf_nodes = [n.nid for n in finished]
         return [(n.parity, n.start, n.end, float(tree.value[n.nid])) for n in finished]
 
     # -- lossguide ----------------------------------------------------------
@@ -817,6 +824,7 @@ class HistGrower:
             evaluate(second, first)
             node_hist.pop(nid, None)
         node_hist.clear()
+        self.leaf_nodes = [n.nid for n in nodes.values()]
         return [(n.parity, n.start, n.end, float(tree.value[n.nid])) for n in nodes.values()]
 
     # -- shared ---------------------------------------------------------------

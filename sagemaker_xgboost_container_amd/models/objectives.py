@@ -11,6 +11,7 @@ Error-message substrings for bad labels intentionally match
 constants/xgb_constants.CUSTOMER_ERRORS so algorithm_mode/train.py maps them
 to UserError (reference train.py:461-467 behavior).
 """
+import json
 import math
 import os
 
@@ -34,6 +35,10 @@ class Objective:
     name = None
     default_metric = "rmse"
     n_outputs = 1
+    # adaptive tree: after a tree of output j is grown, each leaf value is
+    # replaced by eta times the adaptive_alphas[j] quantile of its rows'
+    # residuals (None: the Newton values stay)
+    adaptive_alphas = None
 
     def __init__(self, params=None):
         self.params = params or {}
@@ -248,13 +253,76 @@ class PseudoHuber(Objective):
 
 
 class AbsoluteError(Objective):
+    """reg:absoluteerror. The gradients only shape the tree; its leaves are
+    then the median residual of their rows (adaptive_alphas)."""
+
     name = "reg:absoluteerror"
     default_metric = "mae"
+    adaptive_alphas = [0.5]
 
     def gradients(self, margin, y, weight=None):
         g = torch.sign(margin - y)
         h = torch.ones_like(margin)
         return _pack(g, h, weight)
+
+
+def parse_quantile_alpha(value):
+    """quantile_alpha as a list of floats in (0, 1): a number, a list of
+    numbers, or the string form of either ("0.5", "[0.1, 0.9]", the JSON
+    array string a model file stores)."""
+    if isinstance(value, str):
+        text = value.strip()
+        try:
+            value = json.loads(text) if text.startswith("[") else float(text)
+        except ValueError:
+            raise ValueError(f"quantile_alpha must be a number or a list of numbers, got {value!r}")
+    if isinstance(value, (list, tuple)) or (hasattr(value, "tolist") and getattr(value, "ndim", 0) > 0):
+        items = list(value)
+    else:
+        items = [value]
+    if not items:
+        raise ValueError("quantile_alpha must not be empty")
+    alphas = []
+    for item in items:
+        if isinstance(item, bool) or isinstance(item, str):
+            raise ValueError(f"quantile_alpha must hold numbers, got {item!r}")
+        try:
+            a = float(item)
+        except (TypeError, ValueError):
+            raise ValueError(f"quantile_alpha must hold numbers, got {item!r}")
+        if not (0.0 < a < 1.0):  # also refuses NaN
+            raise ValueError(f"quantile_alpha must lie in (0, 1), got {item!r}")
+        alphas.append(a)
+    return alphas
+
+
+class QuantileError(Objective):
+    """reg:quantileerror — pinball loss, one output per quantile_alpha. The
+    leaves of output j are the alpha_j quantile of their rows' residuals
+    (adaptive_alphas)."""
+
+    name = "reg:quantileerror"
+    default_metric = "quantile"
+
+    def __init__(self, params=None):
+        super().__init__(params)
+        if "quantile_alpha" not in self.params:
+            raise ValueError("reg:quantileerror needs quantile_alpha")
+        self.alphas = parse_quantile_alpha(self.params["quantile_alpha"])
+        self.adaptive_alphas = self.alphas
+        self.n_outputs = len(self.alphas)
+
+    def gradients(self, margin, y, weight=None):
+        # margin: (n,) or (n, k); returns (n, 2) or (n, k, 2)
+        k = self.n_outputs
+        m = margin.reshape(-1, k)
+        alpha = torch.tensor(self.alphas, dtype=torch.float32, device=m.device)
+        g = torch.where(m >= y.reshape(-1, 1), 1.0 - alpha, -alpha).to(torch.float32)
+        h = torch.ones_like(g)
+        gh = torch.stack([g, h], dim=-1)
+        if weight is not None and weight.numel():
+            gh = gh * weight.reshape(-1, 1, 1)
+        return gh[:, 0, :].contiguous() if k == 1 else gh
 
 
 class Softmax(Objective):
@@ -519,6 +587,7 @@ OBJECTIVES = {
         Tweedie,
         PseudoHuber,
         AbsoluteError,
+        QuantileError,
         Softmax,
         SoftmaxLabel,
         RankPairwise,

@@ -13,6 +13,7 @@ the grower. On CPU the same loop runs the torch reference ops (small jobs,
 unit tests).
 """
 import logging
+import math
 
 import numpy as np
 import torch
@@ -38,7 +39,7 @@ _TRAIN_PARAM_KEYS = {
     "interaction_constraints", "deterministic_histogram", "sampling_method", "booster",
     "predictor", "device", "updater", "refresh_leaf", "process_type", "sketch_eps",
     "one_drop", "skip_drop", "rate_drop", "sample_type", "normalize_type", "lambda_bias",
-    "huber_slope", "dsplit", "prob_buffer_row",
+    "huber_slope", "dsplit", "prob_buffer_row", "quantile_alpha",
 }
 
 
@@ -118,6 +119,100 @@ def _csr_tree_margin_fn(csr, device):
     from ..ops.sparse_ref import predict_tree_csr
 
     return lambda tree: predict_tree_csr(tree, csr)
+
+
+class _AdaptiveLeaves:
+    """Adaptive tree leaves (reg:absoluteerror, reg:quantileerror): once a
+    tree's structure is grown, every leaf value becomes eta times the
+    (weighted) alpha quantile of y - margin over the leaf's rows, as
+    upstream XGBoost (1.7 and later) defines these objectives. The rule is
+    ops/torch_ref.leaf_quantiles; on a ROCm device the segmented radix
+    select of csrc/smxgb_quantile.hip computes all leaves at once, and the
+    leaf values are the one readback per tree.
+
+    It sits above the growers and only needs the tree, the node id of
+    every leaf_jobs entry (grower.leaf_nodes) and the rows the tree grew on
+    (grower.tree_rows). Built only for an objective with adaptive_alphas.
+    """
+
+    def __init__(self, objective, X, Xcsr, y, weight, device, comm):
+        self.alphas = list(objective.adaptive_alphas)
+        self.X = X
+        self.Xcsr = Xcsr
+        self.y = y
+        self.weight = weight  # the DMatrix weights, not a sampler's rescaled pairs
+        self.device = device
+        self.comm = comm if comm is not None and getattr(comm, "world_size", 1) > 1 else None
+        self.weight_max = float(weight.max()) if weight is not None and weight.numel() else None
+        if self.weight_max is not None and not (
+            math.isfinite(self.weight_max) and float(weight.min()) >= 0.0
+        ):
+            raise ValueError("sample weights must be finite and non-negative")
+        self._dev_csr = None
+
+    def _leaf_node_of_rows(self, tree):
+        """(n,) node id of the leaf every training row falls into."""
+        if self.device.type == "cuda":
+            from ..ops import hip, hip_sparse
+
+            flat = hip.make_flat_forest([tree], [0], None, self.device)
+            if self.X is not None:
+                return hip.pred_leaf(flat, self.X)[:, 0]
+            if self._dev_csr is None:
+                self._dev_csr = hip_sparse.DeviceCSR(self.Xcsr, self.device)
+            return hip_sparse.pred_leaf_csr(flat, self._dev_csr)[:, 0]
+        if self.X is not None:
+            from ..ops import torch_ref
+
+            return torch_ref.tree_leaf_ids(tree, self.X)
+        from ..ops import sparse_ref
+
+        return sparse_ref.tree_leaf_ids_csr(tree, self.Xcsr)
+
+    def update(self, tree, leaf_jobs, grower, margin_col, cls):
+        """Replace the leaf values of `tree` (an output-`cls` tree grown from
+        the round's margin column `margin_col`) in tree.value and in
+        leaf_jobs; returns the new leaf_jobs (same order)."""
+        leaf_nodes = grower.leaf_nodes
+        n_leaves = len(leaf_nodes)
+        slot_of_node = np.full(tree.num_nodes, -1, dtype=np.int32)
+        slot_of_node[np.asarray(leaf_nodes, dtype=np.int64)] = np.arange(n_leaves, dtype=np.int32)
+        node = self._leaf_node_of_rows(tree).to(self.device)
+        pos = torch.from_numpy(slot_of_node).to(self.device)[node.long()]
+        rows = grower.tree_rows
+        if rows is not None:
+            sampled = torch.full_like(pos, -1)
+            idx = rows.long()
+            sampled[idx] = pos[idx]
+            pos = sampled
+        resid = (self.y - margin_col).to(torch.float32)
+        backend = grower.backend
+        if self.device.type == "cuda":
+            # pos comes from this tree's own leaves and the weights were
+            # checked once: no host check, no synchronization before launch
+            q = backend.leaf_quantiles(
+                pos, resid, n_leaves, self.alphas[cls], self.weight,
+                weight_max=self.weight_max, check=False,
+            )
+        else:
+            q = backend.leaf_quantiles(pos, resid, n_leaves, self.alphas[cls], self.weight)
+        q = q.to(torch.float64)
+        if self.comm is not None:
+            # upstream's rule: the mean of the ranks' local quantiles, over
+            # the ranks where the leaf has rows; one fused allreduce per tree
+            have = ~torch.isnan(q)
+            fused = torch.cat([torch.where(have, q, torch.zeros_like(q)), have.to(torch.float64)])
+            self.comm.allreduce_(fused)
+            q = fused[:n_leaves] / fused[n_leaves:]  # 0 / 0: NaN, no rank has rows
+        q = q.cpu().numpy()  # the tree's one readback
+        values = (q * float(grower.p.eta)).astype(np.float32)
+        out = []
+        for (parity, start, end, value), nid, v in zip(leaf_jobs, leaf_nodes, values):
+            if not np.isnan(v):  # a leaf without rows keeps its Newton value
+                value = float(v)
+                tree.value[nid] = v
+            out.append((parity, start, end, value))
+        return out
 
 
 class _EvalSet:
@@ -370,6 +465,12 @@ def train(
     else:
         grower = HistGrower(qm, params, comm=comm, generator=generator)
 
+    # adaptive tree leaves: only objectives that declare adaptive_alphas
+    # ever build (or run a line of) this step
+    adaptive = None
+    if grower is not None and objective.adaptive_alphas is not None:
+        adaptive = _AdaptiveLeaves(objective, X, Xcsr, y, weight, device, comm)
+
     dart = None
     if booster_kind == "dart":
         dart = {
@@ -468,6 +569,10 @@ def train(
                 and hasattr(grower, "device_async_ok")
                 and grower.device_async_ok()
             )
+            if adaptive is not None:
+                # every tree of the round takes its residuals from the
+                # margin the round began with
+                round_margin = margin.clone() if num_parallel_tree > 1 else margin
             for _parallel in range(num_parallel_tree):
                 if pipeline_classes:
                     handles = [
@@ -476,6 +581,8 @@ def train(
                     ]
                     for cls, handle in enumerate(handles):
                         tree, leaf_jobs = grower.grow_finish(handle)
+                        if adaptive is not None:
+                            leaf_jobs = adaptive.update(tree, leaf_jobs, grower, round_margin[:, cls], cls)
                         add_tree_to_margin(grower.state, tree, leaf_jobs, cls)
                         round_trees.append(tree)
                         round_info.append(cls)
@@ -486,6 +593,8 @@ def train(
                 for cls in range(n_outputs):
                     gh_cls = gh if n_outputs == 1 else gh[:, cls, :].contiguous()
                     tree, leaf_jobs = grower.grow(gh_cls)
+                    if adaptive is not None:
+                        leaf_jobs = adaptive.update(tree, leaf_jobs, grower, round_margin[:, cls], cls)
                     if new_tree_scale != 1.0:
                         leaf_jobs = [(p_, s_, e_, v_ * new_tree_scale) for p_, s_, e_, v_ in leaf_jobs]
                     add_tree_to_margin(grower.state, tree, leaf_jobs, cls, new_tree_scale)

@@ -2631,12 +2631,14 @@ void init_text_parsers(pybind11::module_& m);
 void init_sparse_kernels(pybind11::module_& m);
 void init_shap_compact_kernels(pybind11::module_& m);
 void init_sampling_kernels(pybind11::module_& m);
+void init_quantile_kernels(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_text_parsers(m);
   init_sparse_kernels(m);
   init_shap_compact_kernels(m);
   init_sampling_kernels(m);
+  init_quantile_kernels(m);
   m.def("hist_build", &hist_build, "batched LDS-staged fixed-point histogram build");
   m.def("hist_convert", &hist_convert, "fixed-point -> float32 histogram convert");
   m.def("partition", &partition, "batched two-ended row partition");

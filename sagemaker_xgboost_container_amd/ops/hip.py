@@ -9,6 +9,8 @@ This module raises ImportError loudly when the extension is missing: on a
 GPU box the HIP path must run — there is no silent eager fallback
 (set SMXGB_FORCE_TORCH_OPS=1 explicitly for ablation).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -123,6 +125,89 @@ def gradient_sample(gh, subsample, u):
     out._smxgb_absmax = pmax.amax(dim=0).contiguous()
     rows = keep.nonzero(as_tuple=True)[0].to(torch.int32)
     return rows, out
+
+
+def leaf_quantile_weight_scale(n, weight_max):
+    """Power-of-two fixed-point scale 2^s of the weighted leaf quantile:
+    s = 50 - ceil(log2(n)) - e, with weight_max < 2^e. n weights of at most
+    weight_max then sum below 2^50, so every int64 sum is also exact as a
+    float64."""
+    e_n = (max(int(n), 1) - 1).bit_length()
+    e_w = math.frexp(float(weight_max))[1] if weight_max > 0 else 0
+    return math.ldexp(1.0, 50 - e_n - e_w)
+
+
+def leaf_quantiles(pos, resid, n_leaves, alpha, weight=None, *, weight_max=None, check=True):
+    """Per-leaf (weighted) quantile of `resid` on the device; the rule and
+    the float64 reference are torch_ref.leaf_quantiles. Returns (n_leaves,)
+    float32, NaN for a leaf without rows (or without weight); nothing is
+    read back between the passes of csrc/smxgb_quantile.hip.
+
+    Unweighted results equal the reference bit for bit and do not depend on
+    the row order. Weights are summed in int64 fixed point, w -> round(w *
+    2^s) with 2^s = leaf_quantile_weight_scale(n, max w): also independent
+    of the row order, and exact whenever every w * 2^s is an integer. For
+    arbitrary float32 weights a rounded weight is off by at most half a
+    unit 2^-s, so the returned value v is a residual of the leaf that
+    satisfies the reference's bracket up to slack = n * 2^-s / 2:
+        sum(w[resid <= v]) - alpha * W >= -slack  and
+        sum(w[resid <  v]) - alpha * W <   slack        (W = the leaf's sum).
+
+    `weight_max` (the largest weight, when the caller knows it) and
+    `check=False` (pos and weight already validated) skip the host checks,
+    which cost a synchronization before the first launch.
+    """
+    n_leaves = int(n_leaves)
+    alpha = float(alpha)
+    if not (0.0 < alpha < 1.0):
+        raise ValueError("alpha must be in (0, 1)")
+    if n_leaves < 1 or n_leaves >= 1 << 22:
+        raise ValueError("n_leaves must be in [1, 2^22)")
+    if not pos.is_cuda or pos.dtype != torch.int32 or pos.dim() != 1:
+        raise ValueError("pos must be a 1-d int32 ROCm device tensor")
+    n = pos.numel()
+    if resid.shape != pos.shape or resid.dtype != torch.float32 or resid.device != pos.device:
+        raise ValueError("resid must be a float32 tensor of pos's shape on its device")
+    weighted = weight is not None and weight.numel() > 0
+    if weighted and (weight.shape != pos.shape or weight.device != pos.device):
+        raise ValueError("weight must match pos")
+    dev = pos.device
+    out = torch.full((n_leaves,), float("nan"), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    pos = pos.contiguous()
+    resid = resid.contiguous()
+    w = weight.to(torch.float32).contiguous() if weighted else torch.empty(0, dtype=torch.float32, device=dev)
+    if check or (weighted and weight_max is None):
+        lim = [pos.max().to(torch.float64), pos.min().to(torch.float64)]
+        if weighted:
+            lim += [w.max().to(torch.float64), w.min().to(torch.float64)]
+        lim = torch.stack(lim).tolist()  # the one synchronization, before any launch
+        if lim[0] >= n_leaves or lim[1] < -1:
+            raise ValueError(f"pos must lie in [-1, {n_leaves}): found [{int(lim[1])}, {int(lim[0])}]")
+        if weighted:
+            if not (math.isfinite(lim[2]) and lim[3] >= 0.0):
+                raise ValueError("weights must be finite and non-negative")
+            weight_max = lim[2]
+    scale = leaf_quantile_weight_scale(n, weight_max) if weighted else 1.0
+    i64 = dict(dtype=torch.int64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    none64 = torch.empty(0, **i64)
+    cnt = torch.zeros(n_leaves, **i32)
+    wtot = torch.zeros(n_leaves, **i64) if weighted else none64
+    _K.leaf_quantile_count(pos, w, scale, cnt, wtot)
+    off = torch.cumsum(cnt, 0, dtype=torch.int64) - cnt  # exclusive scan, on the device
+    cursor = torch.zeros(n_leaves, **i32)
+    keys = torch.empty(n, **i32)
+    seg = torch.empty(n, **i32)
+    wq = torch.empty(n, **i64) if weighted else none64
+    _K.leaf_quantile_scatter(pos, resid, w, scale, off, cursor, keys, seg, wq)
+    table = torch.zeros(n_leaves * 256, **i64)
+    state32 = torch.empty(3 * n_leaves, **i32)
+    target = torch.empty(n_leaves, **i64)
+    frac = torch.empty(n_leaves, dtype=torch.float64, device=dev)
+    _K.leaf_quantile_select(keys, seg, wq, off, cnt, wtot, alpha, table, state32, target, frac, out)
+    return out
 
 
 def _padded_words(pairs):

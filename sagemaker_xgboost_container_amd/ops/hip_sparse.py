@@ -53,6 +53,8 @@ find_splits = hip.find_splits
 # gradient-based row sampling reads the dense (n, 2) gradients only
 mvs_threshold = hip.mvs_threshold
 gradient_sample = hip.gradient_sample
+# so does the per-leaf quantile of adaptive tree leaves: (pos, resid, weight)
+leaf_quantiles = hip.leaf_quantiles
 
 # rows of a segment per block. A row costs its stored entries (tens for the
 # wide data this path is for, against f for a dense row), so blocks take

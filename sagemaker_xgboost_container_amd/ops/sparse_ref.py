@@ -393,3 +393,22 @@ def predict_tree_csr(tree, csr, chunk=262144):
         dense[rr, block.indices] = block.data
         out[s:e] = torch_ref.predict_tree(tree, torch.from_numpy(dense))
     return out
+
+
+def tree_leaf_ids_csr(tree, csr, chunk=262144):
+    """(n,) int32 node id of the leaf each row of a scipy CSR matrix falls
+    into — the chunked traversal of predict_tree_csr, for adaptive leaves."""
+    n = csr.shape[0]
+    out = torch.empty(n, dtype=torch.int32)
+    for s in range(0, n, chunk):
+        e = min(s + chunk, n)
+        block = csr[s:e]
+        dense = np.full(block.shape, np.nan, dtype=np.float32)
+        rr = np.repeat(np.arange(block.shape[0]), np.diff(block.indptr))
+        dense[rr, block.indices] = block.data
+        out[s:e] = torch_ref.tree_leaf_ids(tree, torch.from_numpy(dense))
+    return out
+
+
+# the per-leaf quantile reads (pos, resid, weight) only: layout-agnostic
+leaf_quantiles = torch_ref.leaf_quantiles

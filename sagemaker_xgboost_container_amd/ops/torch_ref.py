@@ -261,6 +261,75 @@ def gradient_sample(gh, subsample, u):
     return rows, out
 
 
+def leaf_quantiles(pos, resid, n_leaves, alpha, weight=None):
+    """Per-leaf (weighted) quantile of the residuals: the values adaptive
+    trees (reg:absoluteerror, reg:quantileerror) put into their leaves.
+
+    pos: int32 (n,) leaf slot in [0, n_leaves), or -1 for a row that takes
+    no part; resid: finite float32 (n,). Returns (n_leaves,) float32.
+
+    For a leaf with m rows and sorted residuals v_0 <= ... <= v_{m-1}:
+      m == 0 (or total weight 0)            -> NaN
+      unweighted: alpha <= 1/(m+1)          -> v_0
+                  alpha >= m/(m+1)          -> v_{m-1}
+                  else x = alpha*(m+1), k = floor(x) - 1, d = x - 1 - k,
+                       q = v_k + d * (v_{k+1} - v_k)
+                  (float64 from the float32 values, rounded to float32 once)
+      weighted:   q = v_i for the smallest i with sum_{j<=i} w_j >=
+                  alpha * sum w, clamped to m - 1; no interpolation.
+
+    This float64 sort-based function IS the definition of the rule here. It
+    follows the published description of upstream XGBoost's common::Quantile
+    and WeightedQuantile, but no copy of upstream is available to compare
+    against, so agreement with it in the last bit is not claimed.
+    """
+    import numpy as np
+
+    n_leaves = int(n_leaves)
+    alpha = float(alpha)
+    if not (0.0 < alpha < 1.0):
+        raise ValueError("alpha must be in (0, 1)")
+    p = pos.detach().cpu().numpy().astype(np.int64)
+    r = resid.detach().cpu().numpy().astype(np.float32)
+    if p.shape != r.shape or p.ndim != 1:
+        raise ValueError("pos and resid must be 1-d and of one shape")
+    if p.size and (p.max() >= n_leaves or p.min() < -1):
+        raise ValueError(f"pos must lie in [-1, {n_leaves})")
+    w = None
+    if weight is not None and weight.numel():
+        w = weight.detach().cpu().numpy().astype(np.float32)
+        if w.shape != p.shape:
+            raise ValueError("weight must match pos")
+    order = np.lexsort((r, p))
+    ps, vs = p[order], r[order].astype(np.float64)
+    ws = w[order].astype(np.float64) if w is not None else None
+    lo = np.searchsorted(ps, np.arange(n_leaves), side="left")
+    hi = np.searchsorted(ps, np.arange(n_leaves), side="right")
+    out = np.full(n_leaves, np.nan, dtype=np.float32)
+    for leaf in range(n_leaves):
+        m = int(hi[leaf] - lo[leaf])
+        if m == 0:
+            continue
+        v = vs[lo[leaf]:hi[leaf]]
+        if ws is not None:
+            cs = np.cumsum(ws[lo[leaf]:hi[leaf]])
+            if not cs[-1] > 0.0:
+                continue
+            i = min(int(np.searchsorted(cs, alpha * cs[-1], side="left")), m - 1)
+            out[leaf] = v[i]
+        elif alpha <= 1.0 / (m + 1.0):
+            out[leaf] = v[0]
+        elif alpha >= m / (m + 1.0):
+            out[leaf] = v[m - 1]
+        else:
+            x = alpha * (m + 1.0)
+            k = min(max(int(math.floor(x)) - 1, 0), m - 1)
+            d = (x - 1.0) - k
+            k1 = min(k + 1, m - 1)
+            out[leaf] = np.float32(v[k] + d * (v[k1] - v[k]))
+    return torch.from_numpy(out).to(resid.device)
+
+
 def predict_tree(tree, X):
     """Margin contribution of one tree for dense X (n, f) float32 (NaN missing).
 
@@ -286,6 +355,27 @@ def predict_tree(tree, X):
         node[active] = torch.where(go_left, left[cur], right[cur])
         active = ~is_leaf[node]
     return value[node]
+
+
+def tree_leaf_ids(tree, X):
+    """(n,) int32 node id of the leaf each row of dense X (NaN missing)
+    falls into: predict_tree's traversal, stopping short of the value."""
+    device = X.device
+    node = torch.zeros(X.shape[0], dtype=torch.long, device=device)
+    left = torch.as_tensor(tree.left, device=device, dtype=torch.long)
+    right = torch.as_tensor(tree.right, device=device, dtype=torch.long)
+    feat = torch.as_tensor(tree.feature, device=device, dtype=torch.long)
+    thresh = torch.as_tensor(tree.threshold, device=device, dtype=torch.float32)
+    default_left = torch.as_tensor(tree.default_left, device=device, dtype=torch.bool)
+    is_leaf = left < 0
+    active = ~is_leaf[node]
+    while bool(active.any()):
+        cur = node[active]
+        fv = X[active.nonzero(as_tuple=True)[0], feat[cur]]
+        go_left = torch.where(torch.isnan(fv), default_left[cur], fv < thresh[cur])
+        node[active] = torch.where(go_left, left[cur], right[cur])
+        active = ~is_leaf[node]
+    return node.to(torch.int32)
 
 
 def tree_max_feature(trees):

@@ -46,6 +46,7 @@ setup(
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_sparse.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_shap_compact.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_sampling.hip",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantile.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/text_parsers.cpp",
             ],
             # headers shared by the sources: a change rebuilds the extension
