@@ -232,9 +232,16 @@ class DMatrix:
         base_margin=None,
         qid=None,
         group=None,
+        feature_types=None,
+        enable_categorical=False,
     ):
         self.missing = np.nan if missing is None else missing
         self.feature_names = feature_names
+        # upstream's type strings ("q", "c", "int", "float", "i"), one per
+        # column; only "c" (categorical: the value is a category code)
+        # changes behaviour
+        self.feature_types = list(feature_types) if feature_types is not None else None
+        self.enable_categorical = bool(enable_categorical)
         self._dense = None
         self._csr = None
 
@@ -257,7 +264,7 @@ class DMatrix:
         if hasattr(data, "to_numpy") and hasattr(data, "columns"):
             if self.feature_names is None:
                 self.feature_names = [str(c) for c in data.columns]
-            data = data.to_numpy(dtype=np.float32)
+            data = self._frame_to_numpy(data)
         if label is not None and hasattr(label, "to_numpy"):
             label = label.to_numpy(dtype=np.float32)
 
@@ -287,6 +294,43 @@ class DMatrix:
             raise exc.UserError(
                 f"Label length {len(self._label)} does not match number of rows {self.num_row()}"
             )
+        if self.feature_types is not None and len(self.feature_types) != self.num_col():
+            raise ValueError(
+                f"feature_types has {len(self.feature_types)} entries for {self.num_col()} columns"
+            )
+
+    def _frame_to_numpy(self, frame):
+        """float32 image of a pandas DataFrame. A `category` column becomes
+        its codes (code -1, a missing value, becomes NaN) and is typed "c";
+        it needs enable_categorical, as upstream does."""
+        cat_cols = [i for i, dt in enumerate(frame.dtypes) if str(dt) == "category"]
+        if not cat_cols:
+            return frame.to_numpy(dtype=np.float32)
+        if not self.enable_categorical:
+            raise ValueError(
+                "DataFrame column %r has the category dtype: pass enable_categorical=True "
+                "to train on category codes" % (frame.columns[cat_cols[0]],)
+            )
+        out = np.empty(frame.shape, dtype=np.float32)
+        for i in range(frame.shape[1]):
+            col = frame.iloc[:, i]
+            if i in cat_cols:
+                codes = col.cat.codes.to_numpy().astype(np.float32)
+                codes[codes < 0] = np.nan
+                out[:, i] = codes
+            else:
+                out[:, i] = col.to_numpy(dtype=np.float32)
+        if self.feature_types is None:
+            self.feature_types = ["c" if i in cat_cols else "q" for i in range(frame.shape[1])]
+        return out
+
+    @property
+    def is_cat(self):
+        """Per-column bools, True where feature_types says "c"; None when no
+        column is categorical."""
+        if not self.feature_types or "c" not in self.feature_types:
+            return None
+        return [t == "c" for t in self.feature_types]
 
     # -- shape ------------------------------------------------------------
     def num_row(self):
@@ -384,6 +428,8 @@ class DMatrix:
             weight=self._weight[rindex] if self._weight is not None else None,
             base_margin=self._base_margin[rindex] if self._base_margin is not None else None,
             feature_names=self.feature_names,
+            feature_types=self.feature_types,
+            enable_categorical=self.enable_categorical,
         )
         return out
 
@@ -401,12 +447,21 @@ class DeviceDMatrix:
     trainer consumes.
     """
 
-    def __init__(self, data, label=None, weight=None, feature_names=None, base_margin=None):
+    def __init__(self, data, label=None, weight=None, feature_names=None, base_margin=None,
+                 feature_types=None):
         self._data = data
         self._label = label
         self._weight = weight
         self._base_margin = base_margin
         self.feature_names = feature_names
+        self.feature_types = list(feature_types) if feature_types is not None else None
+
+    @property
+    def is_cat(self):
+        """As DMatrix.is_cat: per-column bools, None without a "c" column."""
+        if not self.feature_types or "c" not in self.feature_types:
+            return None
+        return [t == "c" for t in self.feature_types]
 
     def num_row(self):
         return self._data.shape[0]

@@ -18,7 +18,7 @@ import torch
 
 from .. import ops
 from .objectives import create_objective, parse_quantile_alpha
-from .tree import Tree
+from .tree import CAT_WORDS, Tree, cat_bits_from_members, cat_members
 
 MODEL_VERSION = [3, 0, 5]  # schema-compatible xgboost version
 
@@ -215,6 +215,11 @@ class Booster:
             )
         if ntree_limit:  # legacy alias: trees -> iterations
             iteration_range = (0, int(ntree_limit) // max(1, self._trees_per_round()))
+        if (pred_contribs or pred_interactions) and self.has_categorical_splits():
+            raise NotImplementedError(
+                "pred_contribs, approx_contribs and pred_interactions are not implemented for "
+                "models with categorical splits"
+            )
         if pred_contribs and self._sparse_explain_route(
             data, approx_contribs=approx_contribs, iteration_range=iteration_range
         ):
@@ -295,6 +300,8 @@ class Booster:
             return False
         if self.booster_type not in ("gbtree", "dart"):
             return False
+        if self.has_categorical_splits():
+            return False  # the CSR kernels know no category sets: densify
         csr = data.csr()
         if flag != "1":
             from .trainer import sparse_auto_engage
@@ -305,6 +312,14 @@ class Booster:
             if n * f * 4 <= SPARSE_PREDICT_DENSE_BUDGET:
                 return False
         return bool(csr.has_canonical_format)
+
+    def has_categorical_splits(self):
+        """Does any tree hold a categorical (set-valued) node?"""
+        cache = self._predict_cache if self._predict_cache is not None else {}
+        self._predict_cache = cache
+        if "has_cat" not in cache:
+            cache["has_cat"] = any(getattr(t, "has_categorical", False) for t in self.trees)
+        return cache["has_cat"]
 
     def _predict_sparse(self, data, output_margin, iteration_range, pred_leaf):
         """predict() for a sparse DMatrix without its n x f image.
@@ -618,6 +633,14 @@ class Booster:
             return {name(f): covers[f] / counts[f] for f in counts}
         raise ValueError(f"Unknown importance type: {importance_type}")
 
+    def _refuse_categorical_dump(self, what):
+        """The dump formats print a node as `feature < threshold`; a
+        category set has no such form here."""
+        if self.has_categorical_splits():
+            raise NotImplementedError(
+                f"{what} is not implemented for models with categorical splits"
+            )
+
     def _tree_dump_json(self, tree, with_stats):
         def name(f):
             if self.feature_names and f < len(self.feature_names):
@@ -652,6 +675,8 @@ class Booster:
         """Forest as a pandas DataFrame (xgboost column layout)."""
         import pandas as pd
 
+        self._refuse_categorical_dump("trees_to_dataframe")
+
         rows = []
         for t, tree in enumerate(self.trees):
             for nid in range(tree.num_nodes):
@@ -684,6 +709,7 @@ class Booster:
 
     def get_dump(self, fmap="", with_stats=False, dump_format="text"):
         """Per-tree dumps in the xgboost text or json format."""
+        self._refuse_categorical_dump("get_dump")
         if dump_format == "json":
             return [self._tree_dump_json(t, with_stats) for t in self.trees]
         dumps = []
@@ -822,14 +848,24 @@ class Booster:
     # -- serialization -----------------------------------------------------
     def _tree_to_json(self, tree, tree_id):
         n = tree.num_nodes
+        tree.finalize()
         leaf = tree.left < 0
         split_conditions = np.where(leaf, tree.value, tree.threshold).astype(np.float32)
+        # upstream's layout of the category sets: the members of every
+        # categorical node, flat and ascending, with per-node segments
+        categories, cat_nodes, cat_segments, cat_sizes = [], [], [], []
+        for nid in np.flatnonzero(np.asarray(tree.split_type)):
+            members = cat_members(tree.cat_bits[nid])
+            cat_nodes.append(int(nid))
+            cat_segments.append(len(categories))
+            cat_sizes.append(len(members))
+            categories.extend(members)
         return {
             "base_weights": [float(v) for v in tree.value],
-            "categories": [],
-            "categories_nodes": [],
-            "categories_segments": [],
-            "categories_sizes": [],
+            "categories": categories,
+            "categories_nodes": cat_nodes,
+            "categories_segments": cat_segments,
+            "categories_sizes": cat_sizes,
             "default_left": [int(b) for b in tree.default_left],
             "id": tree_id,
             "left_children": [int(v) for v in tree.left],
@@ -838,7 +874,7 @@ class Booster:
             "right_children": [int(v) for v in tree.right],
             "split_conditions": [float(v) for v in split_conditions],
             "split_indices": [int(v) for v in tree.feature],
-            "split_type": [0] * n,
+            "split_type": [int(v) for v in tree.split_type],
             "sum_hessian": [float(v) for v in tree.sum_hess],
             "tree_param": {
                 "num_deleted": "0",
@@ -853,6 +889,22 @@ class Booster:
         left = np.asarray(obj["left_children"], dtype=np.int32)
         cond = np.asarray(obj["split_conditions"], dtype=np.float32)
         leaf = left < 0
+        # categorical nodes: split_type 1 and a segment of `categories`, the
+        # members of the set that goes right
+        split_type = np.asarray(obj.get("split_type") or np.zeros(len(left)), dtype=np.uint8)
+        split_type = np.where(leaf, 0, split_type).astype(np.uint8)
+        cat_bits = np.zeros((len(left), CAT_WORDS), dtype=np.uint32)
+        if split_type.any():
+            categories = list(obj.get("categories", []))
+            segments = dict(zip(
+                (int(v) for v in obj.get("categories_nodes", [])),
+                zip(obj.get("categories_segments", []), obj.get("categories_sizes", [])),
+            ))
+            for nid in np.flatnonzero(split_type):
+                if int(nid) not in segments:
+                    raise ValueError(f"categorical node {int(nid)} has no entry in categories_nodes")
+                start, size = (int(v) for v in segments[int(nid)])
+                cat_bits[nid] = cat_bits_from_members(categories[start:start + size])
         tree = Tree.from_arrays(
             {
                 "left": left,
@@ -864,6 +916,8 @@ class Booster:
                 "value": np.where(leaf, cond, np.asarray(obj.get("base_weights", cond), dtype=np.float32)),
                 "gain": obj.get("loss_changes", np.zeros(len(left))),
                 "sum_hessian": obj.get("sum_hessian", np.zeros(len(left))),
+                "split_type": split_type,
+                "cat_bits": cat_bits,
             }
         )
         tree.sum_hess = np.asarray(obj.get("sum_hessian", np.zeros(len(left))), dtype=np.float32)
@@ -944,7 +998,7 @@ class Booster:
             "learner": {
                 "attributes": dict(self.attributes_map),
                 "feature_names": self.feature_names or [],
-                "feature_types": [],
+                "feature_types": list(self.feature_types or []),
                 "gradient_booster": self._gradient_booster_json(),
                 "learner_model_param": {
                     "base_score": repr(self.base_score),
@@ -981,6 +1035,7 @@ class Booster:
         self.params["base_score"] = float(lmp.get("base_score", 0.5))
         self.num_features = int(lmp.get("num_feature", 0))
         self.feature_names = learner.get("feature_names") or None
+        self.feature_types = list(learner.get("feature_types") or []) or None
         self.attributes_map = dict(learner.get("attributes", {}))
         self.params["booster"] = booster_name
 

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .tree import Tree
+from .tree import Tree, cat_members
 
 logger = logging.getLogger(__name__)
 
@@ -73,6 +73,12 @@ class GrowParams:
 
             ic = ast.literal_eval(ic) if ic.strip() else None
         self.interaction_constraints = ic
+        # categorical split search: a feature with fewer categories than
+        # max_cat_to_onehot tries one category against the rest, the others
+        # a sorted partition whose smaller side holds at most
+        # max_cat_threshold categories
+        self.max_cat_to_onehot = int(p.get("max_cat_to_onehot", 4))
+        self.max_cat_threshold = int(p.get("max_cat_threshold", 64))
         # Accepted for xgboost parity; this framework is ALWAYS deterministic.
         # A float-atomic LDS fast path for "false" was built and measured
         # 3x SLOWER than the int64 fixed-point slab (80.9 vs 239.4 r/s on the
@@ -127,6 +133,23 @@ class HistGrower:
             if any(mono):
                 self.monotone = torch.tensor(mono, dtype=torch.int8, device=self.device)
                 self._monotone_host = [int(c) for c in mono]
+        # categorical columns (host bools; None without one): their splits
+        # are category sets, searched and partitioned by the per-level path
+        is_cat = getattr(qm, "is_cat", None)
+        self._is_cat_host = [bool(c) for c in is_cat.tolist()] if is_cat is not None else None
+        self._split_kwargs = {}
+        if self._is_cat_host is not None:
+            self._split_kwargs = {
+                "max_cat_to_onehot": self.p.max_cat_to_onehot,
+                "max_cat_threshold": self.p.max_cat_threshold,
+            }
+            if self._monotone_host is not None:
+                for j, (c, m) in enumerate(zip(self._is_cat_host, self._monotone_host)):
+                    if c and m:
+                        raise ValueError(
+                            f"monotone constraint on categorical feature {j}: a category set "
+                            "has no order to constrain"
+                        )
         # "device" or "per_level": which grower path the last tree took
         self.grow_path = None
         # On a backend that declares MIRRORS_DEVICE_GROWER (the HIP backends:
@@ -341,6 +364,8 @@ class HistGrower:
         """Why this configuration cannot use the device grower (None when
         it can)."""
         p = self.p
+        if self._is_cat_host is not None:
+            return "categorical features"
         if p.grow_policy != "depthwise":
             return "grow_policy=%s (lossguide)" % p.grow_policy
         if p.max_leaves != 0:
@@ -455,6 +480,7 @@ class HistGrower:
         # (each tree's rewind depends on its own readback)
         return (
             self.comm is None
+            and self._is_cat_host is None
             and hasattr(self.backend, "DeviceGrower")
             and os.environ.get("SMXGB_NO_DEVICE_GROW") != "1"
             and os.environ.get("SMXGB_PIPELINE") != "v1"
@@ -685,18 +711,21 @@ class HistGrower:
                 min_child_weight=p.min_child_weight,
                 feature_mask=node_feature_mask,
                 monotone=self.monotone,
+                **self._split_kwargs,
             )
             # 3. partition every positive-gain segment against the DEVICE
             # split tensor (no host round-trip before partitioning), then
             # read splits + counts back in a single queue drain
             parity = frontier[0].parity
+            cat_kwargs = {"cat_bits": splits["cat_bits"]} if "cat_bits" in splits else {}
             counters = self.state.partition_level(
                 [node.seg for node in frontier],
                 list(range(len(frontier))),
                 splits["packed"],
                 parity,
+                **cat_kwargs,
             )
-            packed = splits["packed"].cpu().numpy()  # the level's drain
+            packed, cat_sets = self._read_splits(splits)  # the level's drain
             counts = counters[:, 0].cpu().tolist()
             gains = packed[:, 0]
             feats = packed[:, 1].astype(int)
@@ -714,6 +743,7 @@ class HistGrower:
                 lid, rid, lstate, rstate = self._apply_split(
                     tree, node, int(feats[i]), int(bins[i]), bool(dls[i]),
                     float(gains[i]), float(lgs[i]), float(lhs[i]),
+                    cat_bits=cat_sets[i] if cat_sets is not None else None,
                 )
                 mid = node.start + counts[i]
                 mirror = node.sum32 is not None
@@ -768,9 +798,12 @@ class HistGrower:
                 min_child_weight=p.min_child_weight,
                 feature_mask=mask,
                 monotone=self.monotone,
+                **self._split_kwargs,
             )
-            row = s["packed"][0].cpu().numpy()
+            packed_host, cat_host = self._read_splits(s)
+            row = packed_host[0]
             gain = float(row[0])
+            cat_dev = s.get("cat_bits")
             if gain > 0.0:
                 heapq.heappush(
                     heap,
@@ -786,6 +819,8 @@ class HistGrower:
                             "left_h": float(row[5]),
                             "gain": gain,
                             "packed_dev": s["packed"],
+                            "cat_dev": cat_dev,
+                            "cat_bits": cat_host[0] if cat_host is not None else None,
                         },
                     ),
                 )
@@ -799,12 +834,14 @@ class HistGrower:
             node = nodes[nid]
             if p.max_depth and node.depth >= p.max_depth:
                 continue
+            cat_kwargs = {"cat_bits": s["cat_dev"]} if s["cat_dev"] is not None else {}
             counters = self.state.partition_level(
-                [node.seg], [0], s["packed_dev"], node.parity
+                [node.seg], [0], s["packed_dev"], node.parity, **cat_kwargs
             )
             counts = [int(counters[0, 0])]
             lid, rid, lstate, rstate = self._apply_split(
-                tree, node, s["feature"], s["bin"], s["default_left"], s["gain"], s["left_g"], s["left_h"]
+                tree, node, s["feature"], s["bin"], s["default_left"], s["gain"], s["left_g"], s["left_h"],
+                cat_bits=s["cat_bits"],
             )
             mid = node.start + counts[0]
             lnode = _Node(lid, 1 - node.parity, node.start, mid, s["left_g"], s["left_h"],
@@ -828,6 +865,21 @@ class HistGrower:
         return [(n.parity, n.start, n.end, float(tree.value[n.nid])) for n in nodes.values()]
 
     # -- shared ---------------------------------------------------------------
+    @staticmethod
+    def _read_splits(splits):
+        """Host copies (packed [k, 6] float32, cat_bits [k, 8] int32 or None)
+        of a find_splits result in ONE device readback: with categorical
+        columns the two tensors travel as one [k, 14] int32 tensor (an
+        integer copy keeps the float bit patterns)."""
+        packed = splits["packed"]
+        cat_bits = splits.get("cat_bits")
+        if cat_bits is None:
+            return packed.cpu().numpy(), None
+        both = torch.cat(
+            [packed.contiguous().view(torch.int32), cat_bits.to(torch.int32)], dim=1
+        ).cpu().numpy()
+        return np.ascontiguousarray(both[:, :6]).view(np.float32), both[:, 6:]
+
     def _child_weights(self, feature, lower, upper, left_g, left_h, right_g, right_h):
         """Child weights of a split under the parent's monotone weight
         bounds (lower, upper): a constrained feature pins the children to
@@ -850,14 +902,25 @@ class HistGrower:
             wr = self._weight(right_g, right_h, r_lo, r_hi)
         return wl, wr, (l_lo, l_hi), (r_lo, r_hi)
 
-    def _apply_split(self, tree, node, feature, bin_idx, default_left, gain, left_g, left_h):
+    def _apply_split(self, tree, node, feature, bin_idx, default_left, gain, left_g, left_h,
+                     cat_bits=None):
         """Apply one split: node values honor monotone bounds; returns
         (lid, rid, left_state, right_state) where each state is
-        (lower, upper, allowed) for the child _Node."""
+        (lower, upper, allowed) for the child _Node. `cat_bits` is the
+        split's category set, stored on the tree when `feature` is
+        categorical."""
         p = self.p
         GR, HR = node.g - left_g, node.h - left_h
-        cut_base = int(self.qm.cut_ptr[feature])
-        threshold = float(self.qm.cuts[cut_base + bin_idx])
+        if self._is_cat_host is not None and self._is_cat_host[feature]:
+            cat_bits = np.asarray(cat_bits).astype(np.uint32)
+            # the stored condition: the category of a one-hot split, else NaN
+            threshold = float("nan")
+            if self._nbins_host()[feature] < p.max_cat_to_onehot:
+                threshold = float(cat_members(cat_bits)[0])
+        else:
+            cat_bits = None
+            cut_base = int(self.qm.cut_ptr[feature])
+            threshold = float(self.qm.cuts[cut_base + bin_idx])
 
         wl, wr, (l_lo, l_hi), (r_lo, r_hi) = self._child_weights(
             feature, node.lower, node.upper, left_g, left_h, GR, HR
@@ -876,5 +939,12 @@ class HistGrower:
             right_value=wr * p.eta,
             left_hess=left_h,
             right_hess=HR,
+            cat_bits=cat_bits,
         )
         return lid, rid, (l_lo, l_hi, child_allowed), (r_lo, r_hi, child_allowed)
+
+    def _nbins_host(self):
+        nb = getattr(self, "_nbins_list", None)
+        if nb is None:
+            nb = self._nbins_list = [int(v) for v in self.qm.nbins.tolist()]
+        return nb

@@ -13,7 +13,7 @@ one existing tree —
 import numpy as np
 import torch
 
-from ..ops import backend_for
+from ..ops import backend_for, torch_ref
 from .eval_metrics import evaluate as evaluate_metric
 
 
@@ -27,6 +27,7 @@ def _node_stats(tree, X, gh, device):
     feat = torch.as_tensor(np.asarray(tree.feature), device=device, dtype=torch.long)
     thresh = torch.as_tensor(np.asarray(tree.threshold), device=device, dtype=torch.float32)
     dleft = torch.as_tensor(np.asarray(tree.default_left), device=device, dtype=torch.bool)
+    cat = torch_ref.tree_cat_tensors(tree, device)
     n_nodes = tree.num_nodes
 
     G = torch.zeros(n_nodes, dtype=torch.float64, device=device)
@@ -39,7 +40,7 @@ def _node_stats(tree, X, gh, device):
         rows = active.nonzero(as_tuple=True)[0]
         fv = X[rows, feat[cur]]
         missing = torch.isnan(fv)
-        go_left = torch.where(missing, dleft[cur], fv < thresh[cur])
+        go_left = torch.where(missing, dleft[cur], torch_ref.goes_left(fv, thresh, cat, cur))
         nxt = torch.where(go_left, left[cur], right[cur])
         node[active] = nxt
         G.index_add_(0, nxt, gh[rows, 0].to(torch.float64))
@@ -107,7 +108,8 @@ def prune_tree(tree, gamma):
     tree.left = new_left
     tree.right = new_right
     tree.parent = new_parent
-    for name in ("feature", "threshold", "split_bin", "default_left", "value", "gain", "sum_hess"):
+    for name in ("feature", "threshold", "split_bin", "default_left", "value", "gain", "sum_hess",
+                 "split_type", "cat_bits"):
         setattr(tree, name, getattr(tree, name)[idx])
     return tree
 

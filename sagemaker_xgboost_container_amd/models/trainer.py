@@ -40,6 +40,7 @@ _TRAIN_PARAM_KEYS = {
     "predictor", "device", "updater", "refresh_leaf", "process_type", "sketch_eps",
     "one_drop", "skip_drop", "rate_drop", "sample_type", "normalize_type", "lambda_bias",
     "huber_slope", "dsplit", "prob_buffer_row", "quantile_alpha",
+    "max_cat_to_onehot", "max_cat_threshold",
 }
 
 
@@ -78,6 +79,8 @@ def _sparse_path_ok(dtrain, params, device, comm):
         return False
     if not getattr(dtrain, "is_sparse", False):
         return False
+    if getattr(dtrain, "is_cat", None) is not None:
+        return False  # categorical columns train on the dense route
     if device.type not in ("cpu", "cuda"):
         return False
     if device.type == "cuda" and comm is not None:
@@ -344,6 +347,8 @@ def train(
         booster = Booster(params=params, num_features=dtrain.num_col(), feature_names=dtrain.feature_names)
         start_round = 0
     booster.num_features = dtrain.num_col()
+    if getattr(dtrain, "feature_types", None):
+        booster.feature_types = list(dtrain.feature_types)
 
     # -- resident training state ------------------------------------------
     sparse_mode = _sparse_path_ok(dtrain, params, device, comm)
@@ -384,7 +389,10 @@ def train(
                 # (never an n x f matrix) move to the device
                 qm = qm.to(device)
         else:
-            qm = quantize(X, max_bin=max_bin, sample_weight=weight, comm=comm)
+            qm = quantize(
+                X, max_bin=max_bin, sample_weight=weight, comm=comm,
+                is_cat=getattr(dtrain, "is_cat", None), feature_names=dtrain.feature_names,
+            )
     backend = backend_for(device)
 
     base_margin_value = objective.base_margin(booster.base_score)

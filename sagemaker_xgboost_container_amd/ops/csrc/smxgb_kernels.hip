@@ -21,6 +21,7 @@
 
 #include <vector>
 
+#include "smxgb_cat.h"   // CAT_WORDS, cat_bit, cat_goes_left (categorical nodes)
 #include "smxgb_jobs.h"  // WAVE, HIST_BLOCK, CHECK_GPU, HistJob / PartJob / LeafJob
 #include "smxgb_shap.h"  // SHAP_BLOCK, shap_one_fraction, shap_unwound_sum
 
@@ -224,14 +225,19 @@ __global__ __launch_bounds__(HIST_BLOCK) void hist_compact_kernel(
 // missing direction) is read from the on-device packed split tensor
 // ([k, 6] float32 from the split kernels), so no host round-trip sits
 // between split search and partition. gain <= 0 jobs are skipped.
-template <typename BinT>
+// HAS_CAT (a matrix with categorical columns): a split on a feature with
+// is_cat[feature] set sends the bins in the node's category set
+// (cat_bits[node row], smxgb_cat.h) right and the others left.
+template <typename BinT, bool HAS_CAT>
 __global__ __launch_bounds__(HIST_BLOCK) void partition_compact_kernel(
     const BinT* __restrict__ src_bins, const float2* __restrict__ src_gh,
     const int* __restrict__ src_rows, BinT* __restrict__ dst_bins,
     float2* __restrict__ dst_gh, int* __restrict__ dst_rows,
     const PartJob* __restrict__ jobs, const int* __restrict__ block_job,
     const float* __restrict__ split_packed,  // [n_nodes, 6]; job.feature = node row
-    int* __restrict__ counters, int nfeat, int missing_bin) {
+    int* __restrict__ counters, int nfeat, int missing_bin,
+    const unsigned char* __restrict__ is_cat,  // [nfeat]; read only with HAS_CAT
+    const unsigned int* __restrict__ cat_bits) {  // [n_nodes, CAT_WORDS]
   __shared__ int ldest[CPART_TILE];  // destination index per tile row
   __shared__ int lcnt, rcnt, lbase, rbase;
 
@@ -242,6 +248,15 @@ __global__ __launch_bounds__(HIST_BLOCK) void partition_compact_kernel(
   const int feature = (int)sp6[1];
   const int split_bin = (int)sp6[2];
   const int default_left = sp6[3] > 0.5f ? 1 : 0;
+  __shared__ unsigned int cset[CAT_WORDS];  // the node's category set
+  bool cat_split = false;
+  if (HAS_CAT) {
+    cat_split = is_cat[feature] != 0;  // block-uniform
+    if (cat_split && threadIdx.x < CAT_WORDS) {
+      cset[threadIdx.x] = cat_bits[(long long)job.feature * CAT_WORDS + threadIdx.x];
+    }
+    // the tile loop's first barrier orders these stores before any read
+  }
 
   const int chunk = blockIdx.x - job.first_block;
   const long long tile_step = (long long)job.num_blocks * CPART_TILE;
@@ -255,7 +270,13 @@ __global__ __launch_bounds__(HIST_BLOCK) void partition_compact_kernel(
     const int tile_n = (int)min((long long)CPART_TILE, job.end - tile);
     for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
       const int b = (int)src_bins[(tile + i) * (long long)nfeat + feature];
-      const bool left = (b == missing_bin) ? (default_left != 0) : (b <= split_bin);
+      bool left;
+      if (HAS_CAT && cat_split) {
+        left = (b == missing_bin) ? (default_left != 0)
+                                  : !((unsigned)b < (unsigned)CAT_MAX && cat_bit(cset, b));
+      } else {
+        left = (b == missing_bin) ? (default_left != 0) : (b <= split_bin);
+      }
       ldest[i] = left ? atomicAdd(&lcnt, 1) : ~atomicAdd(&rcnt, 1);
     }
     __syncthreads();
@@ -1462,6 +1483,232 @@ __global__ __launch_bounds__(SPLIT_BLOCK) void split_reduce_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// categorical split search (ops/torch_ref.py find_splits states the rule)
+// ---------------------------------------------------------------------------
+//
+// One workgroup per (node, categorical feature); thread t owns category t of
+// the feature's histogram (bin = category code, at most 255 of them). A
+// candidate is a set R of categories that go right:
+//   one-hot (nbins < max_cat_to_onehot): thread t proposes R = {t};
+//   partition: the non-empty categories are bitonic-sorted in LDS by
+//   (g / (h + lambda), category), empty and out-of-range lanes last; after
+//   a Hillis-Steele scan of the sorted sums thread t proposes the cut after
+//   p = t + 1 sorted categories, R being the shorter side.
+// Both missing directions are tried, the block argmax keeps the lowest
+// candidate among equal gains, the winner writes the feature's SplitCand
+// (bin 0) and the block writes the winner's R to cand_bits[node, feat, :]
+// with one ballot per wave. No atomics; every output word has one writer.
+// split_scan_kernel has been launched before with these features masked
+// (gain -1 candidates), split_reduce_kernel runs after over all features.
+__global__ __launch_bounds__(SPLIT_BLOCK) void split_scan_cat_kernel(
+    const float* __restrict__ hist,      // [k, f, stride, 2]
+    const float2* __restrict__ parent,   // [k]
+    const int* __restrict__ nbins,       // [f]
+    const int* __restrict__ cat_feats,   // [n_cat] indices of the categorical features
+    const unsigned char* __restrict__ feat_mask,  // [k*f], [f] or null
+    SplitCand* __restrict__ out,         // [k, f]
+    unsigned int* __restrict__ cand_bits,  // [k, f, CAT_WORDS]
+    int k, int f, int n_cat, int stride, int has_missing, int mask_per_node,
+    float reg_lambda, float reg_alpha, float gamma_, float min_child_weight,
+    int max_cat_to_onehot, int max_cat_threshold) {
+  __shared__ float sg[SPLIT_BLOCK];
+  __shared__ float sh[SPLIT_BLOCK];
+  __shared__ float skey[SPLIT_BLOCK];
+  __shared__ int scat[SPLIT_BLOCK];   // category of a sorted position; bit 8: empty
+  __shared__ int srank[SPLIT_BLOCK];  // sorted position of a category
+  __shared__ float red_gain[SPLIT_BLOCK / WAVE];
+  __shared__ int red_idx[SPLIT_BLOCK / WAVE];
+  __shared__ int win_cand;
+
+  const int node = blockIdx.x / n_cat;
+  const int feat = cat_feats[blockIdx.x % n_cat];
+  const int tid = threadIdx.x;
+  SplitCand best = {-1.0f, 0, 0, 0.f, 0.f};
+  int best_cand = -1;
+
+  bool masked = false;
+  if (feat_mask != nullptr) {
+    masked = feat_mask[mask_per_node ? (node * f + feat) : feat] == 0;
+  }
+  const int nb = nbins[feat];
+  if (nb > SPLIT_BLOCK || nb >= stride + (has_missing ? 0 : 1)) masked = true;
+
+  const float* hbase = hist + (((long long)node * f + feat) * stride) * 2;
+  float g = 0.f, h = 0.f;
+  if (!masked && tid < nb) {
+    g = hbase[tid * 2];
+    h = hbase[tid * 2 + 1];
+  }
+  const bool nonempty = !masked && tid < nb && !(g == 0.f && h == 0.f);
+  const int m = __syncthreads_count(nonempty ? 1 : 0);  // non-empty categories
+  const bool onehot = nb < max_cat_to_onehot;
+
+  if (m >= 2) {  // block-uniform
+    float key = nonempty ? g / (h + reg_lambda) : INFINITY;
+    if (isnan(key)) key = INFINITY;
+    sg[tid] = g;
+    sh[tid] = h;
+    skey[tid] = key;
+    scat[tid] = tid | (nonempty ? 0 : 256);
+    __syncthreads();
+    if (!onehot) {
+      // bitonic sort, ascending by (empty, key, category): a total order
+      for (int size = 2; size <= SPLIT_BLOCK; size <<= 1) {
+        for (int j = size >> 1; j > 0; j >>= 1) {
+          const int other = tid ^ j;
+          if (other > tid) {
+            const int ca = scat[tid], cb = scat[other];
+            const float ka = skey[tid], kb = skey[other];
+            const int ea = ca >> 8, eb = cb >> 8;
+            // does the entry at `other` sort before the one at `tid`?
+            const bool b_first = (eb != ea) ? (eb < ea) : ((kb != ka) ? (kb < ka) : (cb < ca));
+            const bool ascending = (tid & size) == 0;
+            if (b_first == ascending) {
+              const float ga = sg[tid], ha = sh[tid];
+              sg[tid] = sg[other];
+              sh[tid] = sh[other];
+              skey[tid] = kb;
+              scat[tid] = cb;
+              sg[other] = ga;
+              sh[other] = ha;
+              skey[other] = ka;
+              scat[other] = ca;
+            }
+          }
+          __syncthreads();
+        }
+      }
+      srank[scat[tid] & 255] = tid;
+    }
+    // inclusive Hillis-Steele scan of the (sorted) per-category sums
+    for (int ofs = 1; ofs < SPLIT_BLOCK; ofs <<= 1) {
+      float ag = 0.f, ah = 0.f;
+      if (tid >= ofs) {
+        ag = sg[tid - ofs];
+        ah = sh[tid - ofs];
+      }
+      __syncthreads();
+      sg[tid] += ag;
+      sh[tid] += ah;
+      __syncthreads();
+    }
+    const float tot_g = sg[SPLIT_BLOCK - 1];
+    const float tot_h = sh[SPLIT_BLOCK - 1];
+
+    // the left child's sums, missing aside, of this thread's candidate
+    bool valid;
+    float lg0, lh0;
+    if (onehot) {
+      valid = nonempty;
+      lg0 = tot_g - g;
+      lh0 = tot_h - h;
+    } else {
+      const int p = tid + 1;
+      valid = p <= m - 1 && min(p, m - p) <= max_cat_threshold;
+      const bool prefix_right = p <= m - p;
+      lg0 = prefix_right ? tot_g - sg[tid] : sg[tid];
+      lh0 = prefix_right ? tot_h - sh[tid] : sh[tid];
+    }
+    if (valid) {
+      const float2 psum = parent[node];
+      float miss_g = 0.f, miss_h = 0.f;
+      if (has_missing) {
+        miss_g = hbase[(stride - 1) * 2];
+        miss_h = hbase[(stride - 1) * 2 + 1];
+      }
+      const float parent_score = split_score(psum.x, psum.y, reg_alpha, reg_lambda);
+      for (int dir = 0; dir < 2; ++dir) {
+        const float gl = lg0 + (dir ? miss_g : 0.f);
+        const float hl = lh0 + (dir ? miss_h : 0.f);
+        const float gr = psum.x - gl;
+        const float hr = psum.y - hl;
+        if (hl < min_child_weight || hr < min_child_weight) continue;
+        const float gain =
+            0.5f * (split_score(gl, hl, reg_alpha, reg_lambda) +
+                    split_score(gr, hr, reg_alpha, reg_lambda) - parent_score) - gamma_;
+        if (gain > best.gain) {
+          best = {gain, 0, dir, gl, hl};
+          best_cand = tid;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // block argmax, lowest candidate first among equal gains
+  float bg = best.gain;
+  int bidx = tid;
+  for (int ofs = WAVE / 2; ofs > 0; ofs >>= 1) {
+    const float og = __shfl_down(bg, ofs);
+    const int oi = __shfl_down(bidx, ofs);
+    if (og > bg) {
+      bg = og;
+      bidx = oi;
+    }
+  }
+  const int wid = tid / WAVE;
+  if ((tid & (WAVE - 1)) == 0) {
+    red_gain[wid] = bg;
+    red_idx[wid] = bidx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < SPLIT_BLOCK / WAVE; ++w) {
+      if (red_gain[w] > red_gain[0]) {
+        red_gain[0] = red_gain[w];
+        red_idx[0] = red_idx[w];
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == red_idx[0] && best.gain == red_gain[0]) {
+    out[(long long)node * f + feat] = best;
+    win_cand = best_cand;  // -1: the feature has no candidate
+  }
+  __syncthreads();
+
+  // thread t: is category t in the winner's R?
+  const int wc = win_cand;
+  bool member = false;
+  if (wc >= 0 && nonempty) {
+    if (onehot) {
+      member = tid == wc;
+    } else {
+      const int p = wc + 1;
+      const int r = srank[tid];
+      member = (p <= m - p) ? (r < p) : (r >= p && r < m);
+    }
+  }
+  // one 64-bit ballot per wave fills two words: the block's waves cover the set
+  static_assert(SPLIT_BLOCK / WAVE * 2 == CAT_WORDS && SPLIT_BLOCK == CAT_MAX,
+                "split_scan_cat_kernel: one thread per category, two set words per wave");
+  const unsigned long long ballot = __ballot(member ? 1 : 0);
+  if ((tid & (WAVE - 1)) == 0) {
+    unsigned int* bits = cand_bits + ((long long)node * f + feat) * CAT_WORDS;
+    bits[wid * 2] = (unsigned int)(ballot & 0xffffffffull);
+    bits[wid * 2 + 1] = (unsigned int)(ballot >> 32);
+  }
+}
+
+// cat_bits[node] = the winning feature's set when it is categorical and the
+// node splits, else zeros. One thread per node.
+__global__ void split_cat_gather_kernel(const float* __restrict__ packed,  // [k, 6]
+                                        const unsigned char* __restrict__ is_cat,  // [f]
+                                        const unsigned int* __restrict__ cand_bits,
+                                        unsigned int* __restrict__ cat_bits,  // [k, CAT_WORDS]
+                                        int k, int f) {
+  const int node = blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= k) return;
+  const float gain = packed[node * 6];
+  const int feat = (int)packed[node * 6 + 1];
+  const bool cat = gain > 0.f && feat >= 0 && feat < f && is_cat[feat] != 0;
+  for (int w = 0; w < CAT_WORDS; ++w) {
+    cat_bits[node * CAT_WORDS + w] =
+        cat ? cand_bits[((long long)node * f + feat) * CAT_WORDS + w] : 0u;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // row partition (two-ended compaction within each segment)
 // ---------------------------------------------------------------------------
 
@@ -1470,17 +1717,30 @@ __global__ __launch_bounds__(SPLIT_BLOCK) void split_reduce_kernel(
 // ~88 atomics/us even wave-aggregated — measured 2.9 ms/level before).
 #define PART_TILE 4096
 
-template <typename BinT>
+// HAS_CAT: job j on a feature with is_cat set splits by the category set
+// cat_bits[j] (the bins that go right) instead of by split_bin.
+template <typename BinT, bool HAS_CAT>
 __global__ __launch_bounds__(HIST_BLOCK) void partition_kernel(
     const BinT* __restrict__ bins, const int* __restrict__ src, int* __restrict__ dst,
     const PartJob* __restrict__ jobs, const int* __restrict__ block_job,
-    int* __restrict__ counters, int nfeat, int missing_bin) {
+    int* __restrict__ counters, int nfeat, int missing_bin,
+    const unsigned char* __restrict__ is_cat,    // [nfeat]; read only with HAS_CAT
+    const unsigned int* __restrict__ cat_bits) {  // [n_jobs, CAT_WORDS]
   __shared__ int lbuf[PART_TILE];
   __shared__ int rbuf[PART_TILE];
   __shared__ int lcnt, rcnt, lbase, rbase;
+  __shared__ unsigned int cset[CAT_WORDS];  // the job's category set
 
   const int j = block_job[blockIdx.x];
   const PartJob job = jobs[j];
+  bool cat_split = false;
+  if (HAS_CAT) {
+    cat_split = is_cat[job.feature] != 0;  // block-uniform
+    if (cat_split && threadIdx.x < CAT_WORDS) {
+      cset[threadIdx.x] = cat_bits[(long long)j * CAT_WORDS + threadIdx.x];
+    }
+    // the tile loop's first barrier orders these stores before any read
+  }
   const int chunk = blockIdx.x - job.first_block;
   const long long tile_step = (long long)job.num_blocks * PART_TILE;
 
@@ -1494,7 +1754,13 @@ __global__ __launch_bounds__(HIST_BLOCK) void partition_kernel(
     for (int i = threadIdx.x; i < tile_n; i += blockDim.x) {
       const int row = src[tile + i];
       const int b = (int)bins[(long long)row * nfeat + job.feature];
-      const bool left = (b == missing_bin) ? (job.default_left != 0) : (b <= job.split_bin);
+      bool left;
+      if (HAS_CAT && cat_split) {
+        left = (b == missing_bin) ? (job.default_left != 0)
+                                  : !((unsigned)b < (unsigned)CAT_MAX && cat_bit(cset, b));
+      } else {
+        left = (b == missing_bin) ? (job.default_left != 0) : (b <= job.split_bin);
+      }
       if (left) {
         lbuf[atomicAdd(&lcnt, 1)] = row;
       } else {
@@ -1539,6 +1805,22 @@ __global__ __launch_bounds__(HIST_BLOCK) void leaf_update_kernel(
 // thread (measured 1.36 ms for 1k x 500). Each (row, chunk) owns its
 // exclusive out[chunk, row, :] slice — no atomics; the caller reduces the
 // chunk axis with a fixed-order torch sum (deterministic).
+//
+// HAS_CAT (a forest with categorical nodes): cat_slot[node] >= 0 names the
+// node's row of cat_table ([n_cat_nodes, CAT_WORDS]); such a node decides by
+// cat_goes_left (smxgb_cat.h) instead of by its threshold.
+template <bool HAS_CAT>
+__device__ inline bool node_goes_left(float fv, int nid, const float* __restrict__ thresh,
+                                      const int* __restrict__ cat_slot,
+                                      const unsigned int* __restrict__ cat_table) {
+  if (HAS_CAT) {
+    const int slot = cat_slot[nid];
+    if (slot >= 0) return cat_goes_left(fv, cat_table + (long long)slot * CAT_WORDS);
+  }
+  return fv < thresh[nid];
+}
+
+template <bool HAS_CAT>
 __global__ __launch_bounds__(HIST_BLOCK) void predict_kernel(
     const float* __restrict__ X, long long n, int nfeat,
     const int* __restrict__ left, const int* __restrict__ right,
@@ -1546,7 +1828,8 @@ __global__ __launch_bounds__(HIST_BLOCK) void predict_kernel(
     const unsigned char* __restrict__ defl, const float* __restrict__ value,
     const int* __restrict__ tree_root, const int* __restrict__ tree_cls,
     int t_begin, int t_end, float* __restrict__ out, int k, int n_chunks,
-    int trees_per_chunk) {
+    int trees_per_chunk, const int* __restrict__ cat_slot,
+    const unsigned int* __restrict__ cat_table) {
   const long long total = n * (long long)n_chunks;
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -1562,7 +1845,8 @@ __global__ __launch_bounds__(HIST_BLOCK) void predict_kernel(
       int l;
       while ((l = left[nid]) >= 0) {
         const float fv = xr[feat[nid]];
-        const bool goleft = isnan(fv) ? (defl[nid] != 0) : (fv < thresh[nid]);
+        const bool goleft = isnan(fv) ? (defl[nid] != 0)
+                                      : node_goes_left<HAS_CAT>(fv, nid, thresh, cat_slot, cat_table);
         nid = goleft ? l : right[nid];
       }
       orow[tree_cls[t]] += value[nid];
@@ -1573,12 +1857,14 @@ __global__ __launch_bounds__(HIST_BLOCK) void predict_kernel(
 // leaf index per (row, tree): the predict_kernel traversal writing the
 // tree-local leaf id (xgboost pred_leaf semantics). One thread per
 // (row, tree), grid-strided.
+template <bool HAS_CAT>
 __global__ __launch_bounds__(HIST_BLOCK) void pred_leaf_kernel(
     const float* __restrict__ X, long long n, int nfeat,
     const int* __restrict__ left, const int* __restrict__ right,
     const int* __restrict__ feat, const float* __restrict__ thresh,
     const unsigned char* __restrict__ defl, const int* __restrict__ tree_root,
-    int t_begin, int T, int* __restrict__ out) {
+    int t_begin, int T, int* __restrict__ out, const int* __restrict__ cat_slot,
+    const unsigned int* __restrict__ cat_table) {
   const long long total = n * (long long)T;
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -1591,7 +1877,8 @@ __global__ __launch_bounds__(HIST_BLOCK) void pred_leaf_kernel(
     int l;
     while ((l = left[nid]) >= 0) {
       const float fv = xr[feat[nid]];
-      const bool goleft = isnan(fv) ? (defl[nid] != 0) : (fv < thresh[nid]);
+      const bool goleft = isnan(fv) ? (defl[nid] != 0)
+                                    : node_goes_left<HAS_CAT>(fv, nid, thresh, cat_slot, cat_table);
       nid = goleft ? l : right[nid];
     }
     out[idx] = nid - root;
@@ -1800,23 +2087,58 @@ void hist_convert(torch::Tensor in, torch::Tensor out, double inv_g, double inv_
                      n_pairs, (float)inv_g, (float)inv_h);
 }
 
-void partition(torch::Tensor bins, torch::Tensor src, torch::Tensor dst,
-               torch::Tensor jobs, torch::Tensor block_job, torch::Tensor counters,
-               int64_t nfeat, int64_t missing_bin) {
+#define CHECK_GPU_DENSE(x, dt)                                                          \
+  TORCH_CHECK_VALUE(x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt,          \
+                    #x " must be a contiguous ROCm device tensor of the expected dtype")
+
+// the side inputs of a partition with categorical columns: is_cat [nfeat]
+// u8 and one CAT_WORDS-word category set per row of `rows` sets
+static void check_cat_partition(const torch::Tensor& is_cat, const torch::Tensor& cat_bits,
+                                int64_t nfeat, int64_t rows) {
+  CHECK_GPU_DENSE(is_cat, torch::kUInt8);
+  CHECK_GPU_DENSE(cat_bits, torch::kInt32);
+  TORCH_CHECK_VALUE(is_cat.numel() == nfeat, "is_cat must have one entry per feature");
+  TORCH_CHECK_VALUE(cat_bits.numel() >= rows * CAT_WORDS, "cat_bits must be (rows, 8)");
+}
+
+template <bool HAS_CAT>
+static void launch_partition(torch::Tensor bins, torch::Tensor src, torch::Tensor dst,
+                             torch::Tensor jobs, torch::Tensor block_job, torch::Tensor counters,
+                             int64_t nfeat, int64_t missing_bin, const unsigned char* is_cat,
+                             const unsigned int* cat_bits) {
   CHECK_GPU(bins);
   const int grid = (int)block_job.size(0);
   auto stream = current_stream();
   if (bins.scalar_type() == torch::kUInt8) {
-    hipLaunchKernelGGL(partition_kernel<unsigned char>, dim3(grid), dim3(HIST_BLOCK), 0, stream,
-                       bins.data_ptr<unsigned char>(), src.data_ptr<int>(), dst.data_ptr<int>(),
-                       (const PartJob*)jobs.data_ptr<int>(), block_job.data_ptr<int>(),
-                       counters.data_ptr<int>(), (int)nfeat, (int)missing_bin);
+    hipLaunchKernelGGL((partition_kernel<unsigned char, HAS_CAT>), dim3(grid), dim3(HIST_BLOCK), 0,
+                       stream, bins.data_ptr<unsigned char>(), src.data_ptr<int>(),
+                       dst.data_ptr<int>(), (const PartJob*)jobs.data_ptr<int>(),
+                       block_job.data_ptr<int>(), counters.data_ptr<int>(), (int)nfeat,
+                       (int)missing_bin, is_cat, cat_bits);
   } else {
-    hipLaunchKernelGGL(partition_kernel<short>, dim3(grid), dim3(HIST_BLOCK), 0, stream,
+    hipLaunchKernelGGL((partition_kernel<short, HAS_CAT>), dim3(grid), dim3(HIST_BLOCK), 0, stream,
                        bins.data_ptr<short>(), src.data_ptr<int>(), dst.data_ptr<int>(),
                        (const PartJob*)jobs.data_ptr<int>(), block_job.data_ptr<int>(),
-                       counters.data_ptr<int>(), (int)nfeat, (int)missing_bin);
+                       counters.data_ptr<int>(), (int)nfeat, (int)missing_bin, is_cat, cat_bits);
   }
+}
+
+void partition(torch::Tensor bins, torch::Tensor src, torch::Tensor dst,
+               torch::Tensor jobs, torch::Tensor block_job, torch::Tensor counters,
+               int64_t nfeat, int64_t missing_bin) {
+  launch_partition<false>(bins, src, dst, jobs, block_job, counters, nfeat, missing_bin, nullptr,
+                          nullptr);
+}
+
+// partition() for a matrix with categorical columns; cat_bits: one set per job
+void partition_cat(torch::Tensor bins, torch::Tensor src, torch::Tensor dst,
+                   torch::Tensor jobs, torch::Tensor block_job, torch::Tensor counters,
+                   int64_t nfeat, int64_t missing_bin, torch::Tensor is_cat,
+                   torch::Tensor cat_bits) {
+  check_cat_partition(is_cat, cat_bits, nfeat, counters.size(0));
+  launch_partition<true>(bins, src, dst, jobs, block_job, counters, nfeat, missing_bin,
+                         is_cat.data_ptr<unsigned char>(),
+                         (const unsigned int*)cat_bits.data_ptr<int>());
 }
 
 void leaf_update(torch::Tensor buf0, torch::Tensor buf1, torch::Tensor margin_base,
@@ -1828,18 +2150,30 @@ void leaf_update(torch::Tensor buf0, torch::Tensor buf1, torch::Tensor margin_ba
                      (const LeafJob*)jobs.data_ptr<int>(), block_job.data_ptr<int>(), col_stride);
 }
 
-#define CHECK_GPU_DENSE(x, dt)                                                          \
-  TORCH_CHECK_VALUE(x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt,          \
-                    #x " must be a contiguous ROCm device tensor of the expected dtype")
+// The categorical side tables of a flat forest (cat_slot per node, -1 at a
+// numeric node; cat_table [n_cat_nodes, CAT_WORDS]). The slots were built on
+// the host (ops/torch_ref.py flat_cat_arrays) and must lie inside the table:
+// `max_slot` is the host's largest slot.
+static void check_cat_tables(const torch::Tensor& left, const torch::Tensor& cat_slot,
+                             const torch::Tensor& cat_table, int64_t max_slot) {
+  CHECK_GPU_DENSE(cat_slot, torch::kInt32);
+  CHECK_GPU_DENSE(cat_table, torch::kInt32);
+  TORCH_CHECK_VALUE(cat_slot.numel() == left.numel(), "cat_slot must have one entry per node");
+  TORCH_CHECK_VALUE(cat_table.dim() == 2 && cat_table.size(1) == CAT_WORDS,
+                    "cat_table must be (n_cat_nodes, 8)");
+  TORCH_CHECK_VALUE(max_slot < cat_table.size(0), "cat_slot entry outside cat_table");
+}
 
 // Everything is checked on the host before the launch: a matrix narrower
 // than the widest split feature, a class id beyond k or a tree range past
 // the forest would otherwise index device memory out of bounds.
-void predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+template <bool HAS_CAT>
+static void launch_predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                     torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                     torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
                     int64_t t_begin, int64_t t_end, int64_t max_feature, int64_t tree_cls_max,
-                    torch::Tensor out, int64_t k, int64_t n_chunks, int64_t trees_per_chunk) {
+                    torch::Tensor out, int64_t k, int64_t n_chunks, int64_t trees_per_chunk,
+                    const int* cat_slot, const unsigned int* cat_table) {
   CHECK_GPU_DENSE(X, torch::kFloat32);
   CHECK_GPU_DENSE(left, torch::kInt32);
   CHECK_GPU_DENSE(right, torch::kInt32);
@@ -1872,18 +2206,45 @@ void predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
   if (n == 0 || T == 0) return;
   const long long total = n * n_chunks;
   const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 4096);
-  hipLaunchKernelGGL(predict_kernel, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
+  hipLaunchKernelGGL(predict_kernel<HAS_CAT>, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
                      X.data_ptr<float>(), n, (int)X.size(1), left.data_ptr<int>(),
                      right.data_ptr<int>(), feat.data_ptr<int>(), thresh.data_ptr<float>(),
                      defl.data_ptr<unsigned char>(), value.data_ptr<float>(),
                      tree_root.data_ptr<int>(), tree_cls.data_ptr<int>(),
                      (int)t_begin, (int)t_end, out.data_ptr<float>(), (int)k, (int)n_chunks,
-                     (int)trees_per_chunk);
+                     (int)trees_per_chunk, cat_slot, cat_table);
 }
 
-void pred_leaf(torch::Tensor X, torch::Tensor left, torch::Tensor right, torch::Tensor feat,
-               torch::Tensor thresh, torch::Tensor defl, torch::Tensor tree_root,
-               int64_t t_begin, int64_t t_end, int64_t max_feature, torch::Tensor out) {
+void predict_forest(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+                    torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+                    torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
+                    int64_t t_begin, int64_t t_end, int64_t max_feature, int64_t tree_cls_max,
+                    torch::Tensor out, int64_t k, int64_t n_chunks, int64_t trees_per_chunk) {
+  launch_predict_forest<false>(X, left, right, feat, thresh, defl, value, tree_root, tree_cls,
+                               t_begin, t_end, max_feature, tree_cls_max, out, k, n_chunks,
+                               trees_per_chunk, nullptr, nullptr);
+}
+
+// predict_forest() for a forest with categorical nodes
+void predict_forest_cat(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+                        torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+                        torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
+                        int64_t t_begin, int64_t t_end, int64_t max_feature,
+                        int64_t tree_cls_max, torch::Tensor out, int64_t k, int64_t n_chunks,
+                        int64_t trees_per_chunk, torch::Tensor cat_slot, torch::Tensor cat_table,
+                        int64_t max_slot) {
+  check_cat_tables(left, cat_slot, cat_table, max_slot);
+  launch_predict_forest<true>(X, left, right, feat, thresh, defl, value, tree_root, tree_cls,
+                              t_begin, t_end, max_feature, tree_cls_max, out, k, n_chunks,
+                              trees_per_chunk, cat_slot.data_ptr<int>(),
+                              (const unsigned int*)cat_table.data_ptr<int>());
+}
+
+template <bool HAS_CAT>
+static void launch_pred_leaf(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+               torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+               torch::Tensor tree_root, int64_t t_begin, int64_t t_end, int64_t max_feature,
+               torch::Tensor out, const int* cat_slot, const unsigned int* cat_table) {
   CHECK_GPU_DENSE(X, torch::kFloat32);
   CHECK_GPU_DENSE(left, torch::kInt32);
   CHECK_GPU_DENSE(right, torch::kInt32);
@@ -1903,11 +2264,29 @@ void pred_leaf(torch::Tensor X, torch::Tensor left, torch::Tensor right, torch::
   const long long total = n * T;
   if (total == 0) return;
   const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 4096);
-  hipLaunchKernelGGL(pred_leaf_kernel, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
+  hipLaunchKernelGGL(pred_leaf_kernel<HAS_CAT>, dim3(grid), dim3(HIST_BLOCK), 0, current_stream(),
                      X.data_ptr<float>(), n, (int)X.size(1), left.data_ptr<int>(),
                      right.data_ptr<int>(), feat.data_ptr<int>(), thresh.data_ptr<float>(),
                      defl.data_ptr<unsigned char>(), tree_root.data_ptr<int>(), (int)t_begin,
-                     (int)T, out.data_ptr<int>());
+                     (int)T, out.data_ptr<int>(), cat_slot, cat_table);
+}
+
+void pred_leaf(torch::Tensor X, torch::Tensor left, torch::Tensor right, torch::Tensor feat,
+               torch::Tensor thresh, torch::Tensor defl, torch::Tensor tree_root,
+               int64_t t_begin, int64_t t_end, int64_t max_feature, torch::Tensor out) {
+  launch_pred_leaf<false>(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end,
+                          max_feature, out, nullptr, nullptr);
+}
+
+// pred_leaf() for a forest with categorical nodes
+void pred_leaf_cat(torch::Tensor X, torch::Tensor left, torch::Tensor right, torch::Tensor feat,
+                   torch::Tensor thresh, torch::Tensor defl, torch::Tensor tree_root,
+                   int64_t t_begin, int64_t t_end, int64_t max_feature, torch::Tensor out,
+                   torch::Tensor cat_slot, torch::Tensor cat_table, int64_t max_slot) {
+  check_cat_tables(left, cat_slot, cat_table, max_slot);
+  launch_pred_leaf<true>(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end,
+                         max_feature, out, cat_slot.data_ptr<int>(),
+                         (const unsigned int*)cat_table.data_ptr<int>());
 }
 
 // shared argument validation for the two path-form TreeSHAP launchers;
@@ -2035,30 +2414,57 @@ void hist_convert_dev(torch::Tensor in, torch::Tensor out, torch::Tensor gh_max)
                      out.data_ptr<float>(), n_pairs, gh_max.data_ptr<float>());
 }
 
-void partition_compact(torch::Tensor src_bins, torch::Tensor src_gh, torch::Tensor src_rows,
-                       torch::Tensor dst_bins, torch::Tensor dst_gh, torch::Tensor dst_rows,
-                       torch::Tensor jobs, torch::Tensor block_job, torch::Tensor split_packed,
-                       torch::Tensor counters, int64_t nfeat, int64_t missing_bin) {
+template <bool HAS_CAT>
+static void launch_partition_compact(torch::Tensor src_bins, torch::Tensor src_gh,
+                                     torch::Tensor src_rows, torch::Tensor dst_bins,
+                                     torch::Tensor dst_gh, torch::Tensor dst_rows,
+                                     torch::Tensor jobs, torch::Tensor block_job,
+                                     torch::Tensor split_packed, torch::Tensor counters,
+                                     int64_t nfeat, int64_t missing_bin,
+                                     const unsigned char* is_cat, const unsigned int* cat_bits) {
   CHECK_GPU(src_bins);
   const int grid = (int)block_job.size(0);
   auto stream = current_stream();
   if (src_bins.scalar_type() == torch::kUInt8) {
-    hipLaunchKernelGGL(partition_compact_kernel<unsigned char>, dim3(grid), dim3(HIST_BLOCK), 0,
-                       stream, src_bins.data_ptr<unsigned char>(),
+    hipLaunchKernelGGL((partition_compact_kernel<unsigned char, HAS_CAT>), dim3(grid),
+                       dim3(HIST_BLOCK), 0, stream, src_bins.data_ptr<unsigned char>(),
                        (const float2*)src_gh.data_ptr<float>(), src_rows.data_ptr<int>(),
                        dst_bins.data_ptr<unsigned char>(), (float2*)dst_gh.data_ptr<float>(),
                        dst_rows.data_ptr<int>(), (const PartJob*)jobs.data_ptr<int>(),
                        block_job.data_ptr<int>(), split_packed.data_ptr<float>(),
-                       counters.data_ptr<int>(), (int)nfeat, (int)missing_bin);
+                       counters.data_ptr<int>(), (int)nfeat, (int)missing_bin, is_cat, cat_bits);
   } else {
-    hipLaunchKernelGGL(partition_compact_kernel<short>, dim3(grid), dim3(HIST_BLOCK), 0, stream,
-                       src_bins.data_ptr<short>(), (const float2*)src_gh.data_ptr<float>(),
+    hipLaunchKernelGGL((partition_compact_kernel<short, HAS_CAT>), dim3(grid), dim3(HIST_BLOCK), 0,
+                       stream, src_bins.data_ptr<short>(), (const float2*)src_gh.data_ptr<float>(),
                        src_rows.data_ptr<int>(), dst_bins.data_ptr<short>(),
                        (float2*)dst_gh.data_ptr<float>(), dst_rows.data_ptr<int>(),
                        (const PartJob*)jobs.data_ptr<int>(), block_job.data_ptr<int>(),
                        split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)nfeat,
-                       (int)missing_bin);
+                       (int)missing_bin, is_cat, cat_bits);
   }
+}
+
+void partition_compact(torch::Tensor src_bins, torch::Tensor src_gh, torch::Tensor src_rows,
+                       torch::Tensor dst_bins, torch::Tensor dst_gh, torch::Tensor dst_rows,
+                       torch::Tensor jobs, torch::Tensor block_job, torch::Tensor split_packed,
+                       torch::Tensor counters, int64_t nfeat, int64_t missing_bin) {
+  launch_partition_compact<false>(src_bins, src_gh, src_rows, dst_bins, dst_gh, dst_rows, jobs,
+                                  block_job, split_packed, counters, nfeat, missing_bin, nullptr,
+                                  nullptr);
+}
+
+// partition_compact() for a matrix with categorical columns; cat_bits: one
+// category set per row of split_packed
+void partition_compact_cat(torch::Tensor src_bins, torch::Tensor src_gh, torch::Tensor src_rows,
+                           torch::Tensor dst_bins, torch::Tensor dst_gh, torch::Tensor dst_rows,
+                           torch::Tensor jobs, torch::Tensor block_job,
+                           torch::Tensor split_packed, torch::Tensor counters, int64_t nfeat,
+                           int64_t missing_bin, torch::Tensor is_cat, torch::Tensor cat_bits) {
+  check_cat_partition(is_cat, cat_bits, nfeat, split_packed.size(0));
+  launch_partition_compact<true>(src_bins, src_gh, src_rows, dst_bins, dst_gh, dst_rows, jobs,
+                                 block_job, split_packed, counters, nfeat, missing_bin,
+                                 is_cat.data_ptr<unsigned char>(),
+                                 (const unsigned int*)cat_bits.data_ptr<int>());
 }
 
 void leaf_update_compact(torch::Tensor rows0, torch::Tensor rows1, torch::Tensor margin_base,
@@ -2627,6 +3033,76 @@ void find_splits(torch::Tensor hist, torch::Tensor parent, torch::Tensor nbins,
                      (int)f);
 }
 
+// find_splits() for a matrix with categorical columns, on one stream:
+// split_scan_kernel with the categorical features masked out of `num_mask`,
+// split_scan_cat_kernel over (node, categorical feature) with the caller's
+// own mask `cat_mask`, split_reduce_kernel over all features, then the
+// gather of the winners' category sets into cat_bits [k, 8].
+void find_splits_cat(torch::Tensor hist, torch::Tensor parent, torch::Tensor nbins,
+                     torch::Tensor num_mask, int64_t num_mask_per_node, torch::Tensor cat_mask,
+                     int64_t cat_mask_per_node, torch::Tensor monotone, torch::Tensor cands,
+                     torch::Tensor out, torch::Tensor is_cat, torch::Tensor cat_feats,
+                     torch::Tensor cand_bits, torch::Tensor cat_bits, int64_t k, int64_t f,
+                     int64_t stride, int64_t has_missing, double reg_lambda, double reg_alpha,
+                     double gamma_, double min_child_weight, int64_t max_cat_to_onehot,
+                     int64_t max_cat_threshold) {
+  CHECK_GPU_DENSE(hist, torch::kFloat32);
+  CHECK_GPU_DENSE(parent, torch::kFloat32);
+  CHECK_GPU_DENSE(nbins, torch::kInt32);
+  CHECK_GPU_DENSE(num_mask, torch::kUInt8);
+  CHECK_GPU_DENSE(cands, torch::kFloat32);
+  CHECK_GPU_DENSE(out, torch::kFloat32);
+  CHECK_GPU_DENSE(is_cat, torch::kUInt8);
+  CHECK_GPU_DENSE(cat_feats, torch::kInt32);
+  CHECK_GPU_DENSE(cand_bits, torch::kInt32);
+  CHECK_GPU_DENSE(cat_bits, torch::kInt32);
+  const int64_t n_cat = cat_feats.numel();
+  TORCH_CHECK_VALUE(k >= 1 && f >= 1 && n_cat >= 1 && n_cat <= f && stride >= 1,
+                    "bad split-search shape");
+  TORCH_CHECK_VALUE(k * f <= (1ll << 30), "too many (node, feature) pairs");
+  TORCH_CHECK_VALUE(hist.numel() == k * f * stride * 2, "hist must be (k, f * stride, 2)");
+  TORCH_CHECK_VALUE(parent.numel() == k * 2 && nbins.numel() == f && is_cat.numel() == f,
+                    "parent / nbins / is_cat differ from (k, f)");
+  TORCH_CHECK_VALUE(num_mask.numel() == (num_mask_per_node ? k * f : f),
+                    "num_mask must be (f,) or (k, f)");
+  TORCH_CHECK_VALUE(cands.numel() == k * f * 5 && out.numel() == k * 6,
+                    "cands must be (k, f, 5) and out (k, 6)");
+  TORCH_CHECK_VALUE(cand_bits.numel() == k * f * CAT_WORDS && cat_bits.numel() == k * CAT_WORDS,
+                    "cand_bits must be (k, f, 8) and cat_bits (k, 8)");
+  const unsigned char* cat_mask_ptr = nullptr;
+  if (cat_mask.numel()) {
+    CHECK_GPU_DENSE(cat_mask, torch::kUInt8);
+    TORCH_CHECK_VALUE(cat_mask.numel() == (cat_mask_per_node ? k * f : f),
+                      "cat_mask must be (f,) or (k, f)");
+    cat_mask_ptr = cat_mask.data_ptr<unsigned char>();
+  }
+  const signed char* mono_ptr =
+      monotone.numel() ? (const signed char*)monotone.data_ptr<int8_t>() : nullptr;
+  auto stream = current_stream();
+  hipLaunchKernelGGL(split_scan_kernel, dim3((int)(k * f)), dim3(SPLIT_BLOCK), 0, stream,
+                     hist.data_ptr<float>(), (const float2*)parent.data_ptr<float>(),
+                     nbins.data_ptr<int>(), num_mask.data_ptr<unsigned char>(), mono_ptr,
+                     (SplitCand*)cands.data_ptr<float>(), (int)k, (int)f, (int)stride,
+                     (int)has_missing, (int)num_mask_per_node, (float)reg_lambda,
+                     (float)reg_alpha, (float)gamma_, (float)min_child_weight);
+  hipLaunchKernelGGL(split_scan_cat_kernel, dim3((int)(k * n_cat)), dim3(SPLIT_BLOCK), 0, stream,
+                     hist.data_ptr<float>(), (const float2*)parent.data_ptr<float>(),
+                     nbins.data_ptr<int>(), cat_feats.data_ptr<int>(), cat_mask_ptr,
+                     (SplitCand*)cands.data_ptr<float>(),
+                     (unsigned int*)cand_bits.data_ptr<int>(), (int)k, (int)f, (int)n_cat,
+                     (int)stride, (int)has_missing, (int)cat_mask_per_node, (float)reg_lambda,
+                     (float)reg_alpha, (float)gamma_, (float)min_child_weight,
+                     (int)max_cat_to_onehot, (int)max_cat_threshold);
+  hipLaunchKernelGGL(split_reduce_kernel, dim3((int)k), dim3(SPLIT_BLOCK), 0, stream,
+                     (const SplitCand*)cands.data_ptr<float>(), out.data_ptr<float>(), (int)k,
+                     (int)f);
+  hipLaunchKernelGGL(split_cat_gather_kernel, dim3((int)((k + SPLIT_BLOCK - 1) / SPLIT_BLOCK)),
+                     dim3(SPLIT_BLOCK), 0, stream, out.data_ptr<float>(),
+                     is_cat.data_ptr<unsigned char>(),
+                     (const unsigned int*)cand_bits.data_ptr<int>(),
+                     (unsigned int*)cat_bits.data_ptr<int>(), (int)k, (int)f);
+}
+
 void init_text_parsers(pybind11::module_& m);
 void init_sparse_kernels(pybind11::module_& m);
 void init_shap_compact_kernels(pybind11::module_& m);
@@ -2643,6 +3119,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_convert", &hist_convert, "fixed-point -> float32 histogram convert");
   m.def("partition", &partition, "batched two-ended row partition");
   m.def("find_splits", &find_splits, "fused split-gain scan + per-node reduce");
+  m.def("find_splits_cat", &find_splits_cat,
+        "split search with categorical features: numeric scan + category-set scan + reduce");
+  m.def("partition_cat", &partition_cat, "two-ended row partition with category-set splits");
+  m.def("partition_compact_cat", &partition_compact_cat,
+        "compacting partition with category-set splits");
+  m.def("predict_forest_cat", &predict_forest_cat,
+        "batched dense forest traversal with categorical nodes");
+  m.def("pred_leaf_cat", &pred_leaf_cat, "leaf index per (row, tree) with categorical nodes");
   m.def("hist_build_compact", &hist_build_compact, "streaming histogram over compact row buffers");
   m.def("hist_convert_dev", &hist_convert_dev, "fixed-point -> f32 convert with device-resident scale");
   m.def("grow_make_root", &grow_make_root);

@@ -16,6 +16,8 @@
 #include <thread>
 #include <vector>
 
+#include "smxgb_cat.h"  // cat_goes_left: the categorical-node decision
+
 namespace {
 
 struct Chunk {
@@ -185,13 +187,42 @@ static void check_forest_cpu(const torch::Tensor& X, const torch::Tensor& left,
                     " columns but the forest splits on feature ", max_feature);
 }
 
+// The categorical side tables of a flat forest: cat_slot[node] is the node's
+// row of cat_table ([n_cat_nodes, CAT_WORDS]) or -1 at a numeric node.
+static void check_cat_tables(const torch::Tensor& left, const torch::Tensor& cat_slot,
+                             const torch::Tensor& cat_table) {
+  CHECK_HOST_DENSE(cat_slot, torch::kInt32);
+  CHECK_HOST_DENSE(cat_table, torch::kInt32);
+  TORCH_CHECK_VALUE(cat_slot.numel() == left.numel(), "cat_slot must have one entry per node");
+  TORCH_CHECK_VALUE(cat_table.dim() == 2 && cat_table.size(1) == CAT_WORDS,
+                    "cat_table must be (n_cat_nodes, 8)");
+  const int64_t rows = cat_table.size(0);
+  const int* cs = cat_slot.data_ptr<int>();
+  for (int64_t i = 0; i < cat_slot.numel(); ++i) {
+    TORCH_CHECK_VALUE(cs[i] >= -1 && cs[i] < rows, "cat_slot entry outside cat_table");
+  }
+}
+
+// one node's decision for a value that is not NaN
+template <bool HAS_CAT>
+static inline bool node_goes_left(float fv, int nid, const float* tp, const int* cs,
+                                  const unsigned int* ct) {
+  if (HAS_CAT) {
+    const int slot = cs[nid];
+    if (slot >= 0) return cat_goes_left(fv, ct + (int64_t)slot * CAT_WORDS);
+  }
+  return fv < tp[nid];
+}
+
 // Batched forest traversal on host (serving without a GPU): parallel over
 // rows via at::parallel_for (respects torch.set_num_threads / nthread HP).
-void predict_forest_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+template <bool HAS_CAT>
+static void predict_forest_cpu_impl(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                         torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                         torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
                         int64_t t_begin, int64_t t_end, int64_t max_feature,
-                        int64_t tree_cls_max, torch::Tensor out, int64_t k) {
+                        int64_t tree_cls_max, torch::Tensor out, int64_t k,
+                        const int* cs, const unsigned int* ct) {
   check_forest_cpu(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end, max_feature);
   CHECK_HOST_DENSE(value, torch::kFloat32);
   CHECK_HOST_DENSE(tree_cls, torch::kInt32);
@@ -223,13 +254,38 @@ void predict_forest_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right
         int l;
         while ((l = lp[nid]) >= 0) {
           const float fv = xr[fp[nid]];
-          const bool goleft = std::isnan(fv) ? (dp[nid] != 0) : (fv < tp[nid]);
+          const bool goleft =
+              std::isnan(fv) ? (dp[nid] != 0) : node_goes_left<HAS_CAT>(fv, nid, tp, cs, ct);
           nid = goleft ? l : rp[nid];
         }
         orow[cls[t]] += vp[nid];
       }
     }
   });
+}
+
+void predict_forest_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+                        torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+                        torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
+                        int64_t t_begin, int64_t t_end, int64_t max_feature,
+                        int64_t tree_cls_max, torch::Tensor out, int64_t k) {
+  predict_forest_cpu_impl<false>(X, left, right, feat, thresh, defl, value, tree_root, tree_cls,
+                                 t_begin, t_end, max_feature, tree_cls_max, out, k, nullptr,
+                                 nullptr);
+}
+
+// the same traversal over a forest with categorical nodes
+void predict_forest_cat_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+                            torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+                            torch::Tensor value, torch::Tensor tree_root, torch::Tensor tree_cls,
+                            int64_t t_begin, int64_t t_end, int64_t max_feature,
+                            int64_t tree_cls_max, torch::Tensor out, int64_t k,
+                            torch::Tensor cat_slot, torch::Tensor cat_table) {
+  check_cat_tables(left, cat_slot, cat_table);
+  predict_forest_cpu_impl<true>(X, left, right, feat, thresh, defl, value, tree_root, tree_cls,
+                                t_begin, t_end, max_feature, tree_cls_max, out, k,
+                                cat_slot.data_ptr<int>(),
+                                (const unsigned int*)cat_table.data_ptr<int>());
 }
 
 // Multi-threaded CSV parser: numeric fields, empty -> NaN, arbitrary
@@ -543,10 +599,12 @@ void tree_shap_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
 }
 
 // leaf index per (row, tree): vectorized pred_leaf (n, T) int32
-void pred_leaf_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+template <bool HAS_CAT>
+static void pred_leaf_cpu_impl(torch::Tensor X, torch::Tensor left, torch::Tensor right,
                    torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
                    torch::Tensor tree_root, int64_t t_begin, int64_t t_end,
-                   int64_t max_feature, torch::Tensor out) {
+                   int64_t max_feature, torch::Tensor out, const int* cs,
+                   const unsigned int* ct) {
   check_forest_cpu(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end, max_feature);
   CHECK_HOST_DENSE(out, torch::kInt32);
   TORCH_CHECK_VALUE(out.numel() == X.size(0) * (t_end - t_begin), "out must be (n, T)");
@@ -572,13 +630,33 @@ void pred_leaf_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
         int l;
         while ((l = lp[nid]) >= 0) {
           const float fv = xr[fp[nid]];
-          const bool goleft = std::isnan(fv) ? (dp[nid] != 0) : (fv < tp[nid]);
+          const bool goleft =
+              std::isnan(fv) ? (dp[nid] != 0) : node_goes_left<HAS_CAT>(fv, nid, tp, cs, ct);
           nid = goleft ? l : rp[nid];
         }
         orow[t - t_begin] = nid - root;  // tree-local leaf id (xgboost semantics)
       }
     }
   });
+}
+
+void pred_leaf_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+                   torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+                   torch::Tensor tree_root, int64_t t_begin, int64_t t_end,
+                   int64_t max_feature, torch::Tensor out) {
+  pred_leaf_cpu_impl<false>(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end,
+                            max_feature, out, nullptr, nullptr);
+}
+
+void pred_leaf_cat_cpu(torch::Tensor X, torch::Tensor left, torch::Tensor right,
+                       torch::Tensor feat, torch::Tensor thresh, torch::Tensor defl,
+                       torch::Tensor tree_root, int64_t t_begin, int64_t t_end,
+                       int64_t max_feature, torch::Tensor out, torch::Tensor cat_slot,
+                       torch::Tensor cat_table) {
+  check_cat_tables(left, cat_slot, cat_table);
+  pred_leaf_cpu_impl<true>(X, left, right, feat, thresh, defl, tree_root, t_begin, t_end,
+                           max_feature, out, cat_slot.data_ptr<int>(),
+                           (const unsigned int*)cat_table.data_ptr<int>());
 }
 
 void init_text_parsers(pybind11::module_& m) {
@@ -595,4 +673,8 @@ void init_text_parsers(pybind11::module_& m) {
         py::arg("k"), py::arg("max_depth"), py::arg("condition") = 0,
         py::arg("condition_feature") = -1);
   m.def("pred_leaf_cpu", &pred_leaf_cpu, "parallel leaf-index traversal");
+  m.def("predict_forest_cat_cpu", &predict_forest_cat_cpu,
+        "parallel host forest traversal with categorical nodes");
+  m.def("pred_leaf_cat_cpu", &pred_leaf_cat_cpu,
+        "parallel leaf-index traversal with categorical nodes");
 }

@@ -324,8 +324,16 @@ def find_splits(
     min_child_weight=1.0,
     feature_mask=None,
     monotone=None,
+    max_cat_to_onehot=4,
+    max_cat_threshold=64,
 ):
     """Fused HIP split scan: 2 kernel launches per level, zero host syncs.
+
+    A matrix with categorical columns (qm.is_cat) adds two launches: the
+    category-set scan of those features between the numeric scan and the
+    reduce, and the gather of the winners' sets into "cat_bits" [k, 8]
+    int32 (torch_ref.find_splits states the rule). Without such a column
+    nothing else is launched and only "packed" is returned.
 
     Falls back to the torch reference when a feature has > 256 real bins
     (max_bin > 256 configurations)."""
@@ -338,6 +346,12 @@ def find_splits(
         return torch_ref.find_splits(
             hist, parent_sum, qm, reg_lambda=reg_lambda, reg_alpha=reg_alpha, gamma=gamma,
             min_child_weight=min_child_weight, feature_mask=feature_mask, monotone=monotone,
+            max_cat_to_onehot=max_cat_to_onehot, max_cat_threshold=max_cat_threshold,
+        )
+    if getattr(qm, "is_cat", None) is not None:
+        return _find_splits_cat(
+            hist, parent_sum, qm, reg_lambda, reg_alpha, gamma, min_child_weight,
+            feature_mask, monotone, max_cat_to_onehot, max_cat_threshold,
         )
     device = hist.device
     if feature_mask is None:
@@ -361,7 +375,57 @@ def find_splits(
     return {"packed": out}
 
 
-def partition_level(qm, src, dst, segs, feats, split_bins, default_lefts):
+def _cat_tables(qm):
+    """Per-matrix device tables of the categorical columns: is_cat as uint8
+    [f], its complement, and the int32 indices of the set entries."""
+    tables = getattr(qm, "_cat_tables", None)
+    if tables is None:
+        is_cat = qm.is_cat.to(torch.bool)
+        tables = (
+            is_cat.to(torch.uint8).contiguous(),
+            (~is_cat).to(torch.uint8).contiguous(),
+            is_cat.nonzero().flatten().to(torch.int32).contiguous(),
+        )
+        qm._cat_tables = tables
+    return tables
+
+
+def _find_splits_cat(hist, parent_sum, qm, reg_lambda, reg_alpha, gamma, min_child_weight,
+                     feature_mask, monotone, max_cat_to_onehot, max_cat_threshold):
+    k = hist.shape[0]
+    f = qm.num_col
+    device = hist.device
+    is_cat_u8, not_cat_u8, cat_feats = _cat_tables(qm)
+    if feature_mask is None:
+        cat_mask = torch.empty(0, dtype=torch.uint8, device=device)
+        num_mask = not_cat_u8
+        per_node = 0
+    else:
+        cat_mask = feature_mask.to(torch.uint8).contiguous()
+        num_mask = (cat_mask & not_cat_u8).contiguous()  # broadcasts over nodes
+        per_node = 1 if feature_mask.dim() == 2 else 0
+    mono = (
+        monotone.to(torch.int8).contiguous()
+        if monotone is not None
+        else torch.empty(0, dtype=torch.int8, device=device)
+    )
+    cands = torch.empty((k, f, 5), dtype=torch.float32, device=device)
+    out = torch.empty((k, 6), dtype=torch.float32, device=device)
+    cand_bits = torch.empty((k, f, 8), dtype=torch.int32, device=device)
+    cat_bits = torch.empty((k, 8), dtype=torch.int32, device=device)
+    _K.find_splits_cat(
+        hist.contiguous(), parent_sum.contiguous(), qm._nbins_i32, num_mask, per_node,
+        cat_mask, per_node, mono, cands, out, is_cat_u8, cat_feats, cand_bits, cat_bits,
+        k, f, qm.stride, 1 if qm.has_missing else 0,
+        reg_lambda, reg_alpha, gamma, min_child_weight,
+        int(max_cat_to_onehot), int(max_cat_threshold),
+    )
+    return {"packed": out, "cat_bits": cat_bits}
+
+
+def partition_level(qm, src, dst, segs, feats, split_bins, default_lefts, cat_bits=None):
+    """cat_bits: (J, 8) int32 category sets on the device, read for the jobs
+    whose split feature is categorical (qm.is_cat)."""
     J = len(segs)
     packed = []
     blocks_per = []
@@ -376,7 +440,15 @@ def partition_level(qm, src, dst, segs, feats, split_bins, default_lefts):
     block_job = _block_map(blocks_per)
     counters = torch.zeros((J, 2), dtype=torch.int32, device=src.device)
     missing_bin = qm.stride - 1 if qm.has_missing else -1
-    _K.partition(qm.bins, src, dst, jobs_dev, block_job, counters, qm.num_col, missing_bin)
+    if cat_bits is not None and getattr(qm, "is_cat", None) is not None:
+        if tuple(cat_bits.shape) != (J, 8):
+            raise ValueError("cat_bits must hold one (8,) category set per job")
+        _K.partition_cat(
+            qm.bins, src, dst, jobs_dev, block_job, counters, qm.num_col, missing_bin,
+            _cat_tables(qm)[0], cat_bits.to(torch.int32).contiguous(),
+        )
+    else:
+        _K.partition(qm.bins, src, dst, jobs_dev, block_job, counters, qm.num_col, missing_bin)
     return counters[:, 0].cpu().tolist()  # the level's single device sync
 
 
@@ -420,6 +492,22 @@ class _FlatForest:
         self.tree_max_feature = torch_ref.tree_max_feature(trees)
         self.tree_cls_max = int(max(tree_info, default=0))
         self.n_trees = len(trees)
+        self.cat = _flat_cat(trees, device)  # {} for a forest without categorical nodes
+
+
+def _flat_cat(trees, device):
+    """The categorical entries of a flat forest dict: has_cat, cat_slot
+    (int32 per node, -1 at a numeric node), cat_table ([n_cat_nodes, 8]
+    int32 bit patterns) and cat_max_slot; empty without categorical nodes."""
+    has_cat, slot, table = torch_ref.flat_cat_arrays(trees)
+    if not has_cat:
+        return {}
+    return {
+        "has_cat": True,
+        "cat_slot": torch.from_numpy(slot).to(device),
+        "cat_table": torch.from_numpy(table.view(np.int32)).to(device),
+        "cat_max_slot": int(slot.max()),
+    }
 
 
 def _predict_chunking(n, T):
@@ -448,11 +536,15 @@ def _run_predict(X, fl, k, t_begin, t_end):
     if n_chunks == 1:
         tpc = T
     out = torch.zeros((n_chunks, n, k), dtype=torch.float32, device=X.device)
-    _K.predict_forest(
+    args = (
         X.contiguous(), fl["left"], fl["right"], fl["feature"], fl["threshold"],
         fl["default_left"], fl["value"], fl["tree_root"], fl["tree_cls"],
         t_begin, t_end, max_f, int(fl["tree_cls_max"]), out, k, n_chunks, tpc,
     )
+    if fl.get("has_cat"):
+        _K.predict_forest_cat(*args, fl["cat_slot"], fl["cat_table"], fl["cat_max_slot"])
+    else:
+        _K.predict_forest(*args)
     # fixed-order reduce over the chunk axis: deterministic
     return out.sum(0) if n_chunks > 1 else out[0]
 
@@ -467,7 +559,7 @@ def predict_forest(trees, tree_info, X, k, t_begin=0, t_end=None, out=None):
         "threshold": forest.thresh, "default_left": forest.defl, "value": forest.value,
         "tree_root": forest.tree_root, "tree_cls": forest.tree_cls,
         "tree_max_feature": forest.tree_max_feature, "tree_cls_max": forest.tree_cls_max,
-        "n_trees": forest.n_trees,
+        "n_trees": forest.n_trees, **forest.cat,
     }
     res = _run_predict(X, fl, k, t_begin, t_end)
     if out is not None:
@@ -509,6 +601,7 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
         # largest class id: the CSR forest launcher checks it against k
         "tree_cls_max": int(max(tree_info, default=0)),
         "n_trees": len(trees),
+        **_flat_cat(trees, device),
     }
 
 
@@ -578,6 +671,7 @@ def shap_limits(paths, k, nfeat, t_begin, t_end):
 
 
 def _shap_prepare(flat, X, k, t_begin, t_end):
+    torch_ref.refuse_categorical(flat, "device TreeSHAP")
     paths = flat.get("shap_paths")
     if paths is None:
         raise ValueError("flat forest carries no path tables (flat['shap_paths'])")
@@ -757,6 +851,7 @@ def _shap_compact_prepare(flat, X, k, t_begin, t_end):
     from . import hip_sparse as _hs
     from . import shap_paths as _sp
 
+    torch_ref.refuse_categorical(flat, "device TreeSHAP")
     paths = flat.get("shap_paths")
     if paths is None or "host" not in paths:
         raise ValueError("flat forest carries no path tables (flat['shap_paths'])")
@@ -893,10 +988,14 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
         )
     out = torch.zeros((X.shape[0], T), dtype=torch.int32, device=X.device)
     if T > 0 and X.shape[0] > 0:
-        _K.pred_leaf(
+        args = (
             X, flat["left"], flat["right"], flat["feature"], flat["threshold"],
             flat["default_left"], flat["tree_root"], t_begin, t_end, max_f, out,
         )
+        if flat.get("has_cat"):
+            _K.pred_leaf_cat(*args, flat["cat_slot"], flat["cat_table"], flat["cat_max_slot"])
+        else:
+            _K.pred_leaf(*args)
     return out
 
 
@@ -999,13 +1098,15 @@ class TreeState:
         )
         return acc
 
-    def partition_level(self, segs, node_rows, split_packed, src_parity):
+    def partition_level(self, segs, node_rows, split_packed, src_parity, cat_bits=None):
         """Partition every segment whose on-device split has gain > 0.
 
         node_rows[i] = row of segs[i] in split_packed ([k, 6] float32 from
         find_splits, still on device — no host round-trip). Returns the
         DEVICE counters tensor [J, 2]; the caller reads it back together
-        with the packed splits in one drain."""
+        with the packed splits in one drain. cat_bits ([k, 8] int32, the
+        category sets find_splits returned with split_packed) is passed
+        for a matrix with categorical columns."""
         qm = self.qm
         src_bins, src_gh, src_rows = self._src(src_parity)
         dst = 1 - src_parity
@@ -1021,10 +1122,18 @@ class TreeState:
         jobs_dev, block_job = _pack_jobs_and_map(packed, blocks_per)
         counters = torch.zeros((len(segs), 2), dtype=torch.int32, device=src_bins.device)
         missing_bin = qm.stride - 1 if qm.has_missing else -1
-        _K.partition_compact(
+        args = (
             src_bins, src_gh, src_rows, self._bins[dst], self._gh[dst], self._rows[dst],
             jobs_dev, block_job, split_packed.contiguous(), counters, qm.num_col, missing_bin,
         )
+        if cat_bits is not None and getattr(qm, "is_cat", None) is not None:
+            if tuple(cat_bits.shape) != (split_packed.shape[0], 8):
+                raise ValueError("cat_bits must hold one (8,) category set per split row")
+            _K.partition_compact_cat(
+                *args, _cat_tables(qm)[0], cat_bits.to(torch.int32).contiguous()
+            )
+        else:
+            _K.partition_compact(*args)
         if src_parity == 0:
             self._level0 = False
         return counters
@@ -1091,7 +1200,7 @@ class _V1TreeState:
     def build_histograms(self, jobs, parity, scale):
         return build_histograms(self.qm, self.gh, self._bufs[parity], jobs, scale)
 
-    def partition_level(self, segs, node_rows, split_packed, src_parity):
+    def partition_level(self, segs, node_rows, split_packed, src_parity, cat_bits=None):
         sp = split_packed.cpu().numpy()
         counters = torch.zeros((len(segs), 2), dtype=torch.int32)
         do_segs, do_feats, do_bins, do_dls, rows_of = [], [], [], [], []
@@ -1104,9 +1213,15 @@ class _V1TreeState:
             do_dls.append(bool(sp[node_row, 3] > 0.5))
             rows_of.append(j)
         if do_segs:
+            job_bits = None
+            if cat_bits is not None:
+                job_bits = cat_bits[
+                    torch.as_tensor([node_rows[j] for j in rows_of], dtype=torch.long,
+                                    device=cat_bits.device)
+                ]
             counts = partition_level(
                 self.qm, self._bufs[src_parity], self._bufs[1 - src_parity],
-                do_segs, do_feats, do_bins, do_dls,
+                do_segs, do_feats, do_bins, do_dls, job_bits,
             )
             for j, c, (start, end) in zip(rows_of, counts, do_segs):
                 counters[j, 0] = c

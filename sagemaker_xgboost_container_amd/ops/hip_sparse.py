@@ -199,6 +199,8 @@ def predict_tree_csr(tree, csr, device=None):
     if not isinstance(csr, DeviceCSR):
         csr = DeviceCSR(csr, device if device is not None else torch.device("cuda"))
     dev = csr.data.device
+    if getattr(tree, "has_categorical", False):
+        raise NotImplementedError("CSR traversal is not implemented for categorical splits")
     split = tree.left >= 0
     if split.any() and int(tree.feature[split].max()) >= csr.shape[1]:
         raise ValueError("tree splits on a feature the matrix does not have")
@@ -237,6 +239,8 @@ def _check_forest_csr(flat, dcsr, t_begin, t_end):
     resolved t_end. Raises ValueError before anything is launched."""
     if not isinstance(dcsr, DeviceCSR):
         raise ValueError("expected a hip_sparse.DeviceCSR (upload the matrix once, predict many times)")
+    if flat.get("has_cat"):
+        raise NotImplementedError("CSR forest traversal is not implemented for categorical splits")
     if t_end is None:
         t_end = flat["n_trees"]
     if not (0 <= t_begin <= t_end <= flat["n_trees"]):

@@ -22,7 +22,11 @@ import torch
 class QuantizedMatrix:
     """Device-resident quantized features + cut metadata."""
 
-    def __init__(self, bins, cuts, cut_ptr, nbins, stride, has_missing, num_row, num_col):
+    def __init__(self, bins, cuts, cut_ptr, nbins, stride, has_missing, num_row, num_col,
+                 is_cat=None):
+        # (f,) bool on the device, None without a categorical column: such a
+        # column's bin is its category code, nbins = largest code + 1
+        self.is_cat = is_cat
         self.bins = bins            # (n, f) uint8|int16 local bin ids (missing = stride-1)
         self.cuts = cuts            # flat float32 cut values
         self.cut_ptr = cut_ptr      # (f+1,) int64 offsets into cuts
@@ -56,6 +60,7 @@ class QuantizedMatrix:
             self.has_missing,
             self.num_row,
             self.num_col,
+            is_cat=self.is_cat.to(device) if self.is_cat is not None else None,
         )
 
 
@@ -209,15 +214,66 @@ def make_cuts(X, max_bin=256, sample_weight=None):
     return cuts_flat, cut_ptr, nbins.to(X.device)
 
 
-def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=None, comm=None):
+MAX_CAT_CODE = 254  # 255 categories + the missing slot: stride <= 256, uint8 bins
+
+
+def _categorical_cuts(X, cat_cols, cuts, cut_ptr, nbins, comm, feature_names):
+    """Replace the cuts of the categorical columns: nbins = largest code + 1
+    (the global one with a communicator) and cuts 0, 1, ..., nbins - 2, which
+    keep cut_ptr regular and are never read as thresholds. Refuses a value
+    that is not NaN or an integer in [0, MAX_CAT_CODE]."""
+    sub = X[:, cat_cols]
+    present = ~torch.isnan(sub)
+    zeros = torch.zeros_like(sub)
+    vals = torch.where(present, sub, zeros)
+    bad = present & ((vals < 0) | (vals > MAX_CAT_CODE) | (vals != torch.floor(vals)))
+    bad_col = bad.any(0).to(torch.float32)
+    if comm is not None and comm.world_size > 1:
+        # every rank learns of a bad column and raises: none is left waiting
+        # in the collectives that follow
+        comm.allreduce_max_(bad_col)
+    bad_cols = bad_col.nonzero().flatten().tolist()
+    if bad_cols:
+        j = cat_cols[bad_cols[0]]
+        name = feature_names[j] if feature_names else j
+        raise ValueError(
+            f"categorical column {name}: training values must be missing or integers in "
+            f"[0, {MAX_CAT_CODE}]"
+        )
+    top = torch.where(present, sub, zeros - 1).amax(0) if sub.shape[0] else zeros.sum(0) - 1
+    if comm is not None and comm.world_size > 1:
+        comm.allreduce_max_(top)
+    cat_nbins = (top.clamp(min=0) + 1).to(torch.int64)
+    nbins = nbins.clone()
+    nbins[torch.as_tensor(cat_cols, device=nbins.device)] = cat_nbins.to(nbins.device)
+    is_cat_host = set(cat_cols)
+    nb_host = nbins.tolist()
+    pieces = [
+        torch.arange(nb_host[j] - 1, dtype=torch.float32, device=cuts.device)
+        if j in is_cat_host
+        else cuts[int(cut_ptr[j]):int(cut_ptr[j + 1])].to(torch.float32)
+        for j in range(X.shape[1])
+    ]
+    cut_ptr = torch.zeros(X.shape[1] + 1, dtype=torch.int64)
+    cut_ptr[1:] = torch.cumsum(torch.tensor([c.numel() for c in pieces]), 0)
+    return torch.cat(pieces), cut_ptr, nbins
+
+
+def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=None, comm=None,
+             is_cat=None, feature_names=None):
     """Quantize dense X (n, f) float32 with NaN missing into a QuantizedMatrix.
 
     Pass precomputed (cuts, cut_ptr, nbins) to bin an eval/serving matrix
     with training cuts. With a communicator, cuts are computed from the
     GLOBAL distribution (distributed sketch merge) so every rank bins
     identically.
+
+    is_cat: (f,) bools; a True column is categorical: bin = int(value), and
+    its values must be missing or integers in [0, 254] (`feature_names`
+    only names the column in that error).
     """
     n, f = X.shape
+    cat_cols = [j for j, c in enumerate(is_cat) if c] if is_cat is not None else []
     if cuts is None:
         if comm is not None and comm.world_size > 1:
             cuts, cut_ptr, nbins = make_cuts_distributed(
@@ -225,6 +281,10 @@ def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=
             )
         else:
             cuts, cut_ptr, nbins = make_cuts(X, max_bin=max_bin, sample_weight=sample_weight)
+        if cat_cols:
+            cuts, cut_ptr, nbins = _categorical_cuts(
+                X, cat_cols, cuts, cut_ptr, nbins, comm, feature_names
+            )
 
     has_missing = bool(torch.isnan(X).any().item())
     if comm is not None and comm.world_size > 1:
@@ -237,11 +297,17 @@ def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=
     dtype = torch.uint8 if stride <= 256 else torch.int16
 
     bins = torch.empty((n, f), dtype=dtype, device=X.device)
+    cat_set = set(cat_cols)
     for j in range(f):
         col = X[:, j]
         cj = cuts[cut_ptr[j] : cut_ptr[j + 1]]
-        # bin(v) = #cuts <= v
-        b = torch.searchsorted(cj.contiguous(), col.contiguous(), right=True)
+        if j in cat_set:
+            # bin = category code (a code the cuts never saw lands in the
+            # last real bin; training values were range-checked above)
+            b = torch.nan_to_num(col, nan=0.0).to(torch.int64).clamp_(0, max(int(nbins[j]) - 1, 0))
+        else:
+            # bin(v) = #cuts <= v
+            b = torch.searchsorted(cj.contiguous(), col.contiguous(), right=True)
         if has_missing:
             b = torch.where(torch.isnan(col), torch.full_like(b, stride - 1), b)
         bins[:, j] = b.to(dtype)
@@ -255,4 +321,9 @@ def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=
         has_missing=has_missing,
         num_row=n,
         num_col=f,
+        is_cat=(
+            torch.as_tensor([bool(c) for c in is_cat], dtype=torch.bool, device=X.device)
+            if cat_cols
+            else None
+        ),
     )

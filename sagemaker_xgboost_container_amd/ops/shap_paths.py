@@ -43,6 +43,11 @@ def make_shap_paths(trees, tree_info, weight_drop):
     tree_maxf = []
     for t, tree in enumerate(trees):
         tree.finalize()
+        if getattr(tree, "has_categorical", False):
+            # a path element is a threshold interval; a category set is not one
+            raise NotImplementedError(
+                "TreeSHAP path tables are not implemented for models with categorical splits"
+            )
         left = tree.left
         right = tree.right
         feat = tree.feature

@@ -61,6 +61,8 @@ def find_splits(
     min_child_weight=1.0,
     feature_mask=None,
     monotone=None,
+    max_cat_to_onehot=4,
+    max_cat_threshold=64,
 ):
     """Best split per node from per-node histograms.
 
@@ -71,6 +73,25 @@ def find_splits(
     Returns dict of tensors (all shape (k,)):
       feature, bin, gain, default_left, left_g, left_h
     A node with no valid split has gain <= 0.
+
+    Categorical features (qm.is_cat; bin = category code). A candidate is a
+    set R of categories that go right; the others go left, missing goes
+    either way. A category whose (g, h) is (0, 0) is empty and never in R;
+    with fewer than two non-empty categories there is no candidate.
+      one-hot (nbins < max_cat_to_onehot): candidate c is R = {c}.
+      partition: non-empty categories sorted ascending by
+        (g / (h + reg_lambda), category); candidate p - 1, p = 1..m-1, cuts
+        the sorted list after p entries, kept when min(p, m - p) <=
+        max_cat_threshold; R is the shorter side (the prefix when equal).
+    The left sums come from the histogram (everything not in R, plus
+    missing when it goes left), the right sums from parent_sum, as for a
+    numeric feature. Ties go to the lowest candidate, missing-right first.
+    With a categorical column the result also holds "cat_bits": (k, 8) int32,
+    the winner's R (bit c & 31 of word c >> 5), zero for a numeric winner or
+    gain <= 0; column 2 of "packed" is 0 for a categorical winner.
+    As the numerics reference it then also returns "gain64": the winners'
+    gains as float64, before the float32 store (-inf: no candidate). The
+    device backends compute in float32 and have no such value to return.
     """
     k = hist.shape[0]
     f = qm.num_col
@@ -112,6 +133,29 @@ def find_splits(
     if monotone is not None and bool((monotone != 0).any()):
         mono = monotone.to(device).reshape(1, f, 1)
 
+    # categorical features: their rows of the left-sum and validity tables
+    # are indexed by candidate instead of by bin
+    is_cat = getattr(qm, "is_cat", None)
+    cat_feats = is_cat.nonzero().flatten().tolist() if is_cat is not None else []
+    cat_info = {}
+    valid = real_valid.unsqueeze(0)
+    if cat_feats:
+        width = real.shape[2]
+        scan = scan.clone()
+        valid = valid.expand(k, f, width).clone()
+        for j in cat_feats:
+            nbj = min(int(nbins[j]), width)
+            onehot = int(nbins[j]) < int(max_cat_to_onehot)
+            lg, lh, ok, order, nonempty, m = _cat_candidates(
+                real[:, j, :nbj, 0], real[:, j, :nbj, 1], onehot, lam, int(max_cat_threshold)
+            )
+            scan[:, j] = 0.0
+            scan[:, j, :nbj, 0] = lg
+            scan[:, j, :nbj, 1] = lh
+            valid[:, j] = False
+            valid[:, j, :nbj] = ok
+            cat_info[j] = (onehot, order, nonempty, m)
+
     results = []
     for default_left in (False, True):
         gl = scan[..., 0] + (missing[..., 0].unsqueeze(2) if default_left else 0.0)
@@ -119,7 +163,7 @@ def find_splits(
         gr = parent[..., 0] - gl
         hr = parent[..., 1] - hl
         gain = 0.5 * (score(gl, hl) + score(gr, hr) - parent_score) - gamma
-        invalid = (hl < min_child_weight) | (hr < min_child_weight) | ~real_valid.unsqueeze(0)
+        invalid = (hl < min_child_weight) | (hr < min_child_weight) | ~valid
         if mono is not None:
             wl = weight(gl, hl)
             wr = weight(gr, hr)
@@ -153,6 +197,17 @@ def find_splits(
     out_hl = hl.reshape(k, -1).gather(1, idx).squeeze(1)
 
     gain_out = torch.where(torch.isinf(best_gain), torch.full_like(best_gain, -1.0), best_gain).to(torch.float32)
+    cat_bits = None
+    if cat_feats:
+        cat_bits = torch.zeros((k, 8), dtype=torch.int32, device=device)
+        for j, (onehot, order, nonempty, m) in cat_info.items():
+            rows = ((best_feat == j) & (gain_out > 0)).nonzero().flatten()
+            if rows.numel():
+                cat_bits[rows] = _cat_winner_bits(
+                    best_bin[rows], onehot,
+                    None if order is None else order[rows], nonempty[rows], m[rows],
+                )
+            best_bin = torch.where(best_feat == j, torch.zeros_like(best_bin), best_bin)
     packed = torch.stack(
         [
             gain_out,
@@ -164,7 +219,7 @@ def find_splits(
         ],
         dim=1,
     )
-    return {
+    out = {
         "feature": best_feat.to(torch.int32),
         "bin": best_bin.to(torch.int32),
         "gain": gain_out,
@@ -173,27 +228,162 @@ def find_splits(
         "left_h": out_hl.to(torch.float32),
         "packed": packed,
     }
+    if cat_bits is not None:
+        out["cat_bits"] = cat_bits
+        # the winners' gains before the float32 store (-inf: no candidate),
+        # for comparisons at float64 precision
+        out["gain64"] = best_gain
+    return out
 
 
-def _go_left_mask(qm, bins, split_bin, default_left):
+def _cat_candidates(G, H, onehot, lam, max_cat_threshold):
+    """Candidate table of one categorical feature over k nodes (find_splits
+    states the rule). G, H: (k, nb) float64 per-category sums. Returns
+    (left_g, left_h, valid, order, nonempty, m): the left child's sums
+    without missing and the validity of candidate i, (k, nb) each; the
+    sorted category order (None in one-hot mode); the non-empty mask and
+    its count m (k,)."""
+    k, nb = G.shape
+    nonempty = ~((G == 0) & (H == 0))
+    m = nonempty.sum(1)
+    tot_g = G.sum(1, keepdim=True)
+    tot_h = H.sum(1, keepdim=True)
+    if onehot:
+        return tot_g - G, tot_h - H, nonempty & (m >= 2).unsqueeze(1), None, nonempty, m
+    key = G / (H + lam)
+    key = torch.where(torch.isnan(key), torch.full_like(key, float("inf")), key)
+    # ascending by (empty, key, category): two stable passes
+    order = torch.sort(key, dim=1, stable=True).indices
+    empty_sorted = (~nonempty).gather(1, order).to(torch.uint8)
+    order = order.gather(1, torch.sort(empty_sorted, dim=1, stable=True).indices)
+    Gs = G.gather(1, order).cumsum(1)  # column p - 1: the first p sorted
+    Hs = H.gather(1, order).cumsum(1)
+    p = torch.arange(1, nb + 1, device=G.device).unsqueeze(0)
+    mm = m.unsqueeze(1)
+    valid = (p <= mm - 1) & (torch.minimum(p, mm - p) <= max_cat_threshold)
+    prefix_right = p <= mm - p
+    left_g = torch.where(prefix_right, tot_g - Gs, Gs)
+    left_h = torch.where(prefix_right, tot_h - Hs, Hs)
+    return left_g, left_h, valid, order, nonempty, m
+
+
+def _cat_winner_bits(cand, onehot, order, nonempty, m):
+    """(r, 8) int32 category sets R of candidates `cand` (r,) of one
+    categorical feature; order / nonempty / m as _cat_candidates returns."""
+    r, nb = nonempty.shape
+    cats = torch.arange(nb, device=nonempty.device).unsqueeze(0)
+    if onehot:
+        member = cats == cand.unsqueeze(1)
+    else:
+        rank = torch.argsort(order, dim=1)  # position of each category
+        p = (cand + 1).unsqueeze(1)
+        mm = m.unsqueeze(1)
+        member = nonempty & torch.where(p <= mm - p, rank < p, (rank >= p) & (rank < mm))
+    return pack_cat_bits(member)
+
+
+def pack_cat_bits(member):
+    """(r, nb <= 256) bool membership -> (r, 8) int32 bitset words."""
+    r, nb = member.shape
+    full = torch.zeros((r, 256), dtype=torch.int64, device=member.device)
+    full[:, :nb] = member.to(torch.int64)
+    weights = torch.ones(32, dtype=torch.int64, device=member.device) << torch.arange(
+        32, device=member.device
+    )
+    words = (full.reshape(r, 8, 32) * weights).sum(2)
+    words = torch.where(words >= 2**31, words - 2**32, words)  # uint32 pattern as int32
+    return words.to(torch.int32)
+
+
+def cat_bit_of(bits, b):
+    """Is category b (m,) int64 in [0, 256) set in the rows of bits (m, 8)
+    (int32 or wider, the uint32 words' bit patterns)?"""
+    word = bits.to(torch.int64).gather(1, (b >> 5).unsqueeze(1)).squeeze(1)
+    return ((word >> (b & 31)) & 1).to(torch.bool)
+
+
+def cat_goes_left(fv, bits):
+    """Decision at categorical nodes for non-missing values fv (m,) against
+    the sets bits (m, 8): outside [0, 256) left; else the truncated value is
+    the category and members go right (models/tree.py cat_goes_left)."""
+    inside = (fv >= 0) & (fv < 256)
+    c = torch.where(inside, fv, torch.zeros_like(fv)).to(torch.int64)
+    return ~(inside & cat_bit_of(bits, c))
+
+
+def tree_cat_tensors(tree, device):
+    """(slot, table) of a tree for goes_left: slot (num_nodes,) int64, -1 at
+    numeric nodes; table (n_cat_nodes, 8) int64. None without categorical
+    nodes."""
+    import numpy as np
+
+    split_type = np.asarray(getattr(tree, "split_type", ()))
+    if not split_type.any():
+        return None
+    nodes = np.flatnonzero(split_type)
+    slot = np.full(len(split_type), -1, dtype=np.int64)
+    slot[nodes] = np.arange(len(nodes))
+    table = np.stack([np.asarray(tree.cat_bits[i], dtype=np.uint32) for i in nodes])
+    return (
+        torch.from_numpy(slot).to(device),
+        torch.from_numpy(table.astype(np.int64)).to(device),
+    )
+
+
+def flat_cat_tensors(flat):
+    """(slot, table) of a flat forest for goes_left, None when numeric."""
+    if not flat.get("has_cat"):
+        return None
+    return flat["cat_slot"], flat["cat_table"]
+
+
+def goes_left(fv, thresh, cat, cur):
+    """Left/right of non-missing values fv (m,) at nodes cur (m,): the one
+    decision every host traversal uses. cat: None or (slot, table)."""
+    num = fv < thresh[cur]
+    if cat is None:
+        return num
+    slot, table = cat
+    s = slot[cur].long()
+    at_cat = s >= 0
+    return torch.where(at_cat, cat_goes_left(fv, table[s.clamp(min=0)]), num)
+
+
+def refuse_categorical(flat, what):
+    """Explanations are not defined here for set-valued nodes."""
+    if flat.get("has_cat"):
+        raise NotImplementedError(f"{what} is not implemented for models with categorical splits")
+
+
+def _go_left_mask(qm, bins, split_bin, default_left, cat_set=None):
+    """cat_set: (8,) bitset of the bins that go right (categorical split
+    feature), None for a numeric feature's `bin <= split_bin`."""
+    if cat_set is None:
+        real = bins <= int(split_bin)
+    else:
+        inside = bins < 256
+        b = torch.where(inside, bins, torch.zeros_like(bins))
+        real = ~(inside & cat_bit_of(cat_set.reshape(1, 8).expand(bins.numel(), 8), b))
     if qm.has_missing:
         is_missing = bins == (qm.stride - 1)
-        return torch.where(
-            is_missing,
-            torch.full_like(is_missing, bool(default_left)),
-            bins <= int(split_bin),
-        )
-    return bins <= int(split_bin)
+        return torch.where(is_missing, torch.full_like(is_missing, bool(default_left)), real)
+    return real
 
 
-def partition_level(qm, src, dst, segs, feats, split_bins, default_lefts):
+def partition_level(qm, src, dst, segs, feats, split_bins, default_lefts, cat_bits=None):
     """Partition each (start, end) segment of src into dst (left block then
-    right block in the same index range). Returns list of left counts."""
+    right block in the same index range). Returns list of left counts.
+    cat_bits: (J, 8) category sets, read for the jobs whose split feature is
+    categorical (qm.is_cat)."""
     counts = []
-    for (start, end), feature, sbin, dl in zip(segs, feats, split_bins, default_lefts):
+    is_cat = getattr(qm, "is_cat", None)
+    for j, ((start, end), feature, sbin, dl) in enumerate(zip(segs, feats, split_bins, default_lefts)):
         rows = src[start:end]
         bins = qm.bins[rows.long(), int(feature)].long()
-        go_left = _go_left_mask(qm, bins, sbin, dl)
+        cat_set = None
+        if cat_bits is not None and is_cat is not None and bool(is_cat[int(feature)]):
+            cat_set = cat_bits[j]
+        go_left = _go_left_mask(qm, bins, sbin, dl, cat_set)
         left = rows[go_left]
         right = rows[~go_left]
         dst[start : start + left.numel()] = left
@@ -345,13 +535,14 @@ def predict_tree(tree, X):
     default_left = torch.as_tensor(tree.default_left, device=device, dtype=torch.bool)
     is_leaf = left < 0
     value = torch.as_tensor(tree.value, device=device, dtype=torch.float32)
+    cat = tree_cat_tensors(tree, device)
 
     active = ~is_leaf[node]
     while bool(active.any()):
         cur = node[active]
         fv = X[active.nonzero(as_tuple=True)[0], feat[cur]]
         missing = torch.isnan(fv)
-        go_left = torch.where(missing, default_left[cur], fv < thresh[cur])
+        go_left = torch.where(missing, default_left[cur], goes_left(fv, thresh, cat, cur))
         node[active] = torch.where(go_left, left[cur], right[cur])
         active = ~is_leaf[node]
     return value[node]
@@ -368,11 +559,12 @@ def tree_leaf_ids(tree, X):
     thresh = torch.as_tensor(tree.threshold, device=device, dtype=torch.float32)
     default_left = torch.as_tensor(tree.default_left, device=device, dtype=torch.bool)
     is_leaf = left < 0
+    cat = tree_cat_tensors(tree, device)
     active = ~is_leaf[node]
     while bool(active.any()):
         cur = node[active]
         fv = X[active.nonzero(as_tuple=True)[0], feat[cur]]
-        go_left = torch.where(torch.isnan(fv), default_left[cur], fv < thresh[cur])
+        go_left = torch.where(torch.isnan(fv), default_left[cur], goes_left(fv, thresh, cat, cur))
         node[active] = torch.where(go_left, left[cur], right[cur])
         active = ~is_leaf[node]
     return node.to(torch.int32)
@@ -409,11 +601,47 @@ def check_predict_args(flat, X, k, t_begin, t_end, classes=True):
     return max_f
 
 
-def make_flat_forest(trees, tree_info, weight_drop, device):
-    """Flatten trees into device arrays with global node ids; leaf values
-    pre-scaled by weight_drop (dart)."""
+def flat_cat_arrays(trees):
+    """Categorical part of a flat forest, on the host: (has_cat, slot,
+    table). slot: int32 per global node, the node's row of table or -1 at a
+    numeric node; table: (n_cat_nodes, 8) uint32 category sets. A forest
+    without categorical nodes gets (False, None, None)."""
     import numpy as np
 
+    types = [np.asarray(getattr(t, "split_type", ()), dtype=np.uint8) for t in trees]
+    if not any(ty.any() for ty in types):
+        return False, None, None
+    split_type = np.concatenate(
+        [ty if ty.size else np.zeros(t.num_nodes, np.uint8) for ty, t in zip(types, trees)]
+    )
+    nodes = np.flatnonzero(split_type)
+    slot = np.full(split_type.size, -1, dtype=np.int32)
+    slot[nodes] = np.arange(nodes.size, dtype=np.int32)
+    bits = np.concatenate(
+        [
+            np.asarray(t.cat_bits, dtype=np.uint32).reshape(-1, 8)
+            if ty.any()
+            else np.zeros((t.num_nodes, 8), np.uint32)
+            for ty, t in zip(types, trees)
+        ]
+    )
+    return True, slot, np.ascontiguousarray(bits[nodes])
+
+
+def make_flat_forest(trees, tree_info, weight_drop, device):
+    """Flatten trees into device arrays with global node ids; leaf values
+    pre-scaled by weight_drop (dart). A forest with categorical nodes also
+    carries has_cat / cat_slot / cat_table (flat_cat_arrays)."""
+    import numpy as np
+
+    has_cat, cat_slot, cat_table = flat_cat_arrays(trees)
+    cat = {}
+    if has_cat:
+        cat = {
+            "has_cat": True,
+            "cat_slot": torch.from_numpy(cat_slot.astype(np.int64)).to(device),
+            "cat_table": torch.from_numpy(cat_table.astype(np.int64)).to(device),
+        }
     offsets = np.cumsum([0] + [t.num_nodes for t in trees]).astype(np.int64)
     left = np.concatenate([t.left + (t.left >= 0) * offsets[i] for i, t in enumerate(trees)])
     right = np.concatenate([t.right + (t.right >= 0) * offsets[i] for i, t in enumerate(trees)])
@@ -437,6 +665,7 @@ def make_flat_forest(trees, tree_info, weight_drop, device):
         "tree_cls_max": int(max(tree_info, default=0)),
         "max_depth": max((t.max_depth() for t in trees), default=0),
         "n_trees": len(trees),
+        **cat,
     }
 
 
@@ -444,23 +673,18 @@ def _native_predict(flat, X, k, t_begin, t_end, max_f):
     """Parallel C++ traversal (serving hot path on CPU hosts)."""
     from . import _smxgb_hip as K
 
-    if "_i32" not in flat:
-        flat["_i32"] = {
-            "left": flat["left"].to(torch.int32).contiguous(),
-            "right": flat["right"].to(torch.int32).contiguous(),
-            "feature": flat["feature"].to(torch.int32).contiguous(),
-            "default_left": flat["default_left"].to(torch.uint8).contiguous(),
-            "tree_root": flat["tree_root"].to(torch.int32).contiguous(),
-            "tree_cls": flat["tree_cls"].to(torch.int32).contiguous(),
-        }
-    f = flat["_i32"]
+    f = _flat_i32(flat)
     out = torch.zeros((X.shape[0], k), dtype=torch.float32)
-    K.predict_forest_cpu(
+    args = (
         X.contiguous(), f["left"], f["right"], f["feature"],
         flat["threshold"].contiguous(), f["default_left"], flat["value"].contiguous(),
         f["tree_root"], f["tree_cls"], t_begin, t_end, max_f, int(flat["tree_cls_max"]),
         out, k,
     )
+    if flat.get("has_cat"):
+        K.predict_forest_cat_cpu(*args, f["cat_slot"], f["cat_table"])
+    else:
+        K.predict_forest_cpu(*args)
     return out
 
 
@@ -486,6 +710,7 @@ def predict_forest_flat(flat, X, k, t_begin=0, t_end=None):
     feat = flat["feature"]
     thresh = flat["threshold"]
     defl = flat["default_left"]
+    cat = flat_cat_tensors(flat)
     active = left[node] >= 0
     while bool(active.any()):
         cur = node[active]
@@ -493,7 +718,7 @@ def predict_forest_flat(flat, X, k, t_begin=0, t_end=None):
         rows = active.nonzero(as_tuple=True)[0]
         fv = X[rows, fidx]
         missing = torch.isnan(fv)
-        go_left = torch.where(missing, defl[cur], fv < thresh[cur])
+        go_left = torch.where(missing, defl[cur], goes_left(fv, thresh, cat, cur))
         node[active] = torch.where(go_left, left[cur], right[cur])
         active = left[node] >= 0
     out.index_add_(1, flat["tree_cls"][t_begin:t_end], flat["value"][node])
@@ -519,9 +744,10 @@ class TreeState:
     def build_histograms(self, jobs, parity, scale):
         return build_histograms(self.qm, self.gh, self._bufs[parity], jobs, scale)
 
-    def partition_level(self, segs, node_rows, split_packed, src_parity):
-        """Same contract as the HIP state: consume the packed split tensor,
-        skip gain <= 0 jobs, return a [J, 2] counters tensor."""
+    def partition_level(self, segs, node_rows, split_packed, src_parity, cat_bits=None):
+        """Same contract as the HIP state: consume the packed split tensor
+        (and, with categorical columns, the [k, 8] category sets of the same
+        rows), skip gain <= 0 jobs, return a [J, 2] counters tensor."""
         sp = split_packed.detach().cpu().numpy()
         counters = torch.zeros((len(segs), 2), dtype=torch.int32)
         do_segs, do_feats, do_bins, do_dls, rows_of = [], [], [], [], []
@@ -533,9 +759,14 @@ class TreeState:
             do_bins.append(int(sp[node_row, 2]))
             do_dls.append(bool(sp[node_row, 3] > 0.5))
             rows_of.append(j)
+        job_bits = None
+        if cat_bits is not None and rows_of:
+            job_bits = cat_bits[
+                torch.as_tensor([node_rows[j] for j in rows_of], dtype=torch.long, device=cat_bits.device)
+            ]
         counts = partition_level(
             self.qm, self._bufs[src_parity], self._bufs[1 - src_parity],
-            do_segs, do_feats, do_bins, do_dls,
+            do_segs, do_feats, do_bins, do_dls, job_bits,
         )
         for j, c, (start, end) in zip(rows_of, counts, do_segs):
             counters[j, 0] = c
@@ -566,6 +797,11 @@ def _flat_i32(flat):
             "tree_root": flat["tree_root"].to(torch.int32).contiguous(),
             "tree_cls": flat["tree_cls"].to(torch.int32).contiguous(),
         }
+        if flat.get("has_cat"):
+            table = flat["cat_table"]
+            table = torch.where(table >= 2**31, table - 2**32, table)  # uint32 pattern as int32
+            flat["_i32"]["cat_slot"] = flat["cat_slot"].to(torch.int32).contiguous()
+            flat["_i32"]["cat_table"] = table.to(torch.int32).contiguous()
     return flat["_i32"]
 
 
@@ -729,6 +965,7 @@ def tree_shap(flat, X, k, t_begin=0, t_end=None, condition=0, condition_feature=
     `condition` = +1 / -1 computes Lundberg's conditional contributions
     with `condition_feature` fixed on / off (the building block of the
     interaction values); the default 0 is plain TreeSHAP."""
+    refuse_categorical(flat, "TreeSHAP")
     if t_end is None:
         t_end = flat["n_trees"]
     X = X.cpu().contiguous()
@@ -791,6 +1028,7 @@ def tree_shap_interactions(flat, X, k, t_begin=0, t_end=None):
     features the forest never splits on interact with nothing. The diagonal
     is phi_i - sum_{j != i} phi_int[i, j]; the bias row/column stay zero
     (the booster fills cell [f, f])."""
+    refuse_categorical(flat, "TreeSHAP interactions")
     if t_end is None:
         t_end = flat["n_trees"]
     n, f = X.shape
@@ -814,6 +1052,7 @@ def saabas_contribs(flat, X, k, t_begin=0, t_end=None):
     (n, k, f+1) float64. Walking each (row, tree) root -> leaf, the change
     of the node expectation value[next] - value[cur] is credited to the
     split feature; the bias column collects the root values."""
+    refuse_categorical(flat, "Saabas attribution")
     if t_end is None:
         t_end = flat["n_trees"]
     n, f = X.shape
@@ -888,11 +1127,15 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
         from . import _smxgb_hip as K
 
         i32 = _flat_i32(flat)
-        K.pred_leaf_cpu(
+        args = (
             X, i32["left"], i32["right"], i32["feature"],
             flat["threshold"].contiguous(), i32["default_left"],
             i32["tree_root"], t_begin, t_end, max_f, out,
         )
+        if flat.get("has_cat"):
+            K.pred_leaf_cat_cpu(*args, i32["cat_slot"], i32["cat_table"])
+        else:
+            K.pred_leaf_cpu(*args)
         return out
     except ImportError:
         pass
@@ -903,6 +1146,7 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
     thresh = flat["threshold"]
     defl = flat["default_left"]
     roots = flat["tree_root"][t_begin:t_end]
+    cat = flat_cat_tensors(flat)
     node = roots.unsqueeze(0).expand(n, T).contiguous()
     active = left[node] >= 0
     while bool(active.any()):
@@ -910,7 +1154,9 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
         fv = X[active.any(dim=1).nonzero(as_tuple=True)[0], :] if False else None  # noqa
         rows = active.nonzero(as_tuple=True)[0]
         fvals = X[rows, feat[nid]]
-        goleft = torch.where(torch.isnan(fvals), defl[nid].to(torch.bool), fvals < thresh[nid])
+        goleft = torch.where(
+            torch.isnan(fvals), defl[nid].to(torch.bool), goes_left(fvals, thresh, cat, nid)
+        )
         node[active] = torch.where(goleft, left[nid], right[nid]).to(node.dtype)
         active = left[node] >= 0
     return (node - roots.unsqueeze(0)).to(torch.int32)

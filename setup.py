@@ -51,6 +51,7 @@ setup(
             ],
             # headers shared by the sources: a change rebuilds the extension
             depends=[
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_cat.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_jobs.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_shap.h",
             ],

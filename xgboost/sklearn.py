@@ -17,6 +17,8 @@ _ALIASES = {
     "reg_lambda": "lambda",
     "min_split_loss": "gamma",
 }
+# constructor arguments that describe the data, not the training run
+_DATA_KWARGS = ("enable_categorical", "feature_types")
 
 
 class XGBModel:
@@ -49,10 +51,25 @@ class XGBModel:
     def _train_params(self):
         params = {"objective": self.objective}
         for k, v in self.kwargs.items():
-            if v is None:
+            if v is None or k in _DATA_KWARGS:
                 continue
             params[_ALIASES.get(k, k)] = v
         return params
+
+    def _dmatrix(self, X, **kwargs):
+        """DMatrix of X with the estimator's enable_categorical /
+        feature_types; a DataFrame with `category` columns goes in whole so
+        that the columns become category codes (or are refused without
+        enable_categorical)."""
+        enable = bool(self.kwargs.get("enable_categorical", False))
+        has_category = hasattr(X, "dtypes") and hasattr(X, "columns") and any(
+            str(dt) == "category" for dt in X.dtypes
+        )
+        data = X if has_category else _as_array(X)
+        return DMatrix(
+            data, enable_categorical=enable, feature_types=self.kwargs.get("feature_types"),
+            **kwargs,
+        )
 
     # -- core --------------------------------------------------------------
     def fit(self, X, y, sample_weight=None, eval_set=None, verbose=False,
@@ -66,12 +83,11 @@ class XGBModel:
                 params["objective"] = "multi:softprob"
             if str(params.get("objective", "")).startswith("multi"):
                 params["num_class"] = self.n_classes_
-        dtrain = DMatrix(_as_array(X), label=np.asarray(y, dtype=np.float32),
-                         weight=sample_weight)
+        dtrain = self._dmatrix(X, label=np.asarray(y, dtype=np.float32), weight=sample_weight)
         evals = []
         if eval_set:
             evals = [
-                (DMatrix(_as_array(ex), label=np.asarray(ey, dtype=np.float32)), f"validation_{i}")
+                (self._dmatrix(ex, label=np.asarray(ey, dtype=np.float32)), f"validation_{i}")
                 for i, (ex, ey) in enumerate(eval_set)
             ]
         maximize = None
@@ -105,8 +121,13 @@ class XGBModel:
 
     def predict(self, X, output_margin=False, iteration_range=None):
         return self.get_booster().predict(
-            _as_array(X), output_margin=output_margin, iteration_range=iteration_range
+            self._predict_data(X), output_margin=output_margin, iteration_range=iteration_range
         )
+
+    def _predict_data(self, X):
+        if self.kwargs.get("enable_categorical") or self.kwargs.get("feature_types"):
+            return self._dmatrix(X)
+        return _as_array(X)
 
     def save_model(self, path):
         self.get_booster().save_model(path)
@@ -149,14 +170,14 @@ class XGBClassifier(XGBModel):
     _default_objective = "binary:logistic"
 
     def predict_proba(self, X):
-        raw = self.get_booster().predict(_as_array(X))
+        raw = self.get_booster().predict(self._predict_data(X))
         if raw.ndim == 1:
             return np.stack([1.0 - raw, raw], axis=1)
         return raw
 
     def predict(self, X, output_margin=False, iteration_range=None):
         raw = self.get_booster().predict(
-            _as_array(X), output_margin=output_margin, iteration_range=iteration_range
+            self._predict_data(X), output_margin=output_margin, iteration_range=iteration_range
         )
         if output_margin:
             return raw
@@ -177,7 +198,7 @@ class XGBRanker(XGBModel):
 
     def fit(self, X, y, group=None, qid=None, **kwargs):
         params = self._train_params()
-        dtrain = DMatrix(_as_array(X), label=np.asarray(y, dtype=np.float32))
+        dtrain = self._dmatrix(X, label=np.asarray(y, dtype=np.float32))
         if group is not None:
             dtrain.set_group(group)
         elif qid is not None:
