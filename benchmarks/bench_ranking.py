@@ -1,0 +1,112 @@
+"""Ranking gradient on an MSLR-like set: the sampled pair method (one random
+partner per document, a Python loop over the query groups) against the
+top-k LambdaRank kernels of csrc/smxgb_rank.hip, in one process.
+
+    python benchmarks/bench_ranking.py [--rows 2400000] [--reps 3] [--rounds 3]
+
+Prints one JSON line: gradient milliseconds per call of each path (median
+and spread over the alternating repetitions) and depth-6 training rounds
+per second with each path. Needs an MI355X.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from sagemaker_xgboost_container_amd.data.dmatrix import DMatrix  # noqa: E402
+from sagemaker_xgboost_container_amd.models import trainer  # noqa: E402
+from sagemaker_xgboost_container_amd.models.objectives import create_objective  # noqa: E402
+
+
+def make_data(rows, features, seed):
+    """Seeded, MSLR-like: group sizes in [1, 1300] with a mean near 120
+    (lognormal), labels 0-4 that depend on a few features."""
+    rng = np.random.default_rng(seed)
+    sizes = []
+    left = rows
+    while left > 0:
+        m = int(min(left, np.clip(rng.lognormal(mean=4.45, sigma=0.8), 1, 1300)))
+        sizes.append(m)
+        left -= m
+    X = rng.standard_normal((rows, features), dtype=np.float32)
+    rel = X[:, 0] + 0.5 * X[:, 1] - 0.5 * X[:, 2] + rng.standard_normal(rows, dtype=np.float32)
+    y = np.clip(np.floor(rel + 1.5), 0, 4).astype(np.float32)
+    return X, y, sizes
+
+
+def time_gradients(objective, margin, y, reps):
+    out = []
+    for _ in range(reps):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        start.record()
+        objective.gradients(margin, y, None)
+        end.record()
+        torch.cuda.synchronize()
+        out.append(start.elapsed_time(end))
+    return out
+
+
+def time_training(params, dtrain, rounds):
+    """Seconds per round: (rounds + 1)-round run minus a 1-round run, so that
+    the set-up (upload, quantisation) cancels."""
+    def run(r):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        trainer.train(params, dtrain, num_boost_round=r, verbose_eval=False)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    one = run(1)
+    return (run(rounds + 1) - one) / rounds
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=2_400_000)
+    ap.add_argument("--features", type=int, default=136)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=7)
+    args = ap.parse_args()
+    X, y, sizes = make_data(args.rows, args.features, args.seed)
+    dtrain = DMatrix(X, label=y)
+    dtrain.set_group(sizes)
+    dev = torch.device("cuda")
+    yd = torch.from_numpy(y).to(dev)
+    # margins of a partly trained model: labels plus noise, so ranks are mixed
+    margin = (yd * 0.5 + torch.randn(args.rows, device=dev, generator=torch.Generator(dev).manual_seed(1)))
+    paths = {
+        "sampled": {"objective": "rank:ndcg"},
+        "topk": {"objective": "rank:ndcg", "lambdarank_pair_method": "topk"},
+    }
+    objectives = {}
+    for name, p in paths.items():
+        objectives[name] = create_objective(p["objective"], p)
+        objectives[name].set_info(dtrain, dev)
+        objectives[name].gradients(margin, yd, None)  # warm-up (plan, allocator)
+    grad_ms = {name: [] for name in paths}
+    for _ in range(args.reps):  # alternate: both paths see the same machine state
+        for name in paths:
+            grad_ms[name] += time_gradients(objectives[name], margin, yd, 1)
+    result = {"rows": args.rows, "groups": len(sizes), "mean_group": args.rows / len(sizes)}
+    for name, p in paths.items():
+        ms = grad_ms[name]
+        sec = time_training(dict(p, max_depth=6, eta=0.3, device="cuda"), dtrain, args.rounds)
+        result[name] = {
+            "grad_ms_median": statistics.median(ms), "grad_ms_min": min(ms), "grad_ms_max": max(ms),
+            "round_s": sec, "rounds_per_s": 1.0 / sec,
+            "grad_share_of_round": statistics.median(ms) / 1e3 / sec,
+        }
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

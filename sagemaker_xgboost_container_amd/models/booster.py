@@ -52,6 +52,10 @@ def objective_params_from_json(obj_json, params):
             ("lambdarank_num_pair_per_sample", int),
             ("lambdarank_pair_method", str),
             ("lambdarank_unbiased", int),
+            # written with lambdarank_pair_method=topk only
+            ("lambdarank_normalization", int),
+            ("lambdarank_score_normalization", int),
+            ("ndcg_exp_gain", int),
         ),
     }
     for block_name, fields in blocks.items():
@@ -963,6 +967,15 @@ class Booster:
                 "lambdarank_pair_method": str(p.get("lambdarank_pair_method", "mean")),
                 "lambdarank_unbiased": str(p.get("lambdarank_unbiased", 0)),
             }
+            if str(p.get("lambdarank_pair_method", "mean")) == "topk":
+                # the top-k path's own settings; files of every other
+                # configuration stay as they were
+                block = obj["lambdarank_param"]
+                block["lambdarank_num_pair_per_sample"] = str(
+                    p.get("lambdarank_num_pair_per_sample", 32))
+                for key in ("lambdarank_normalization", "lambdarank_score_normalization",
+                            "ndcg_exp_gain"):
+                    block[key] = str(int(p.get(key, 1)))
         return obj
 
     def _gbtree_model_json(self):

@@ -383,9 +383,39 @@ class _RankObjective(Objective):
     def __init__(self, params=None):
         super().__init__(params)
         self.group_ptr = None  # (G+1,) int64 boundaries
+        p = self.params
+        self.pair_method = str(p.get("lambdarank_pair_method", "mean"))
+        self._plan = None  # device work tables of the topk path, built once
+        # Only parsed here: a Booster builds its objective to predict too,
+        # and a loaded model may carry settings that training refuses
+        # (_check_training_params, reached from set_info).
+        if self.pair_method == "topk":
+            self.num_pair = int(p.get("lambdarank_num_pair_per_sample", 32))
+            self.normalization = bool(int(p.get("lambdarank_normalization", 1)))
+            self.score_normalization = bool(int(p.get("lambdarank_score_normalization", 1)))
+            self.exp_gain = bool(int(p.get("ndcg_exp_gain", 1)))
+
+    def validate_labels(self, y):
+        if self.pair_method == "topk":
+            from ..ops import torch_ref
+
+            torch_ref.check_lambdarank_labels(y, self.name)
+
+    def _check_training_params(self):
+        if self.pair_method not in ("mean", "topk"):
+            raise ValueError(
+                f"lambdarank_pair_method must be 'mean' or 'topk', got {self.pair_method!r}"
+            )
+        if self.pair_method == "topk":
+            if int(self.params.get("lambdarank_unbiased", 0) or 0):
+                raise ValueError("lambdarank_unbiased=1 is not implemented")
+            if not (1 <= self.num_pair <= 4096):
+                raise ValueError("lambdarank_num_pair_per_sample must be in [1, 4096]")
 
     def set_info(self, dmatrix, device):
+        self._check_training_params()
         group = dmatrix.get_group() if hasattr(dmatrix, "get_group") else None
+        self._plan = None
         if group is not None:
             import numpy as np
 
@@ -394,10 +424,36 @@ class _RankObjective(Objective):
         else:
             self.group_ptr = None
 
+    def _topk_gradients(self, margin, y, weight):
+        """lambdarank_pair_method=topk: the HIP kernels on a ROCm device,
+        the float64 reference elsewhere (or under SMXGB_FORCE_TORCH_OPS=1)."""
+        from ..ops import torch_ref
+
+        if not margin.is_cuda or os.environ.get("SMXGB_FORCE_TORCH_OPS") == "1":
+            return torch_ref.lambdarank_gradients(
+                margin, y, self.group_ptr, weight, self.name, self.num_pair,
+                self.normalization, self.score_normalization, self.exp_gain,
+            )
+        from ..ops import hip as _hip  # raises if the extension is missing on GPU
+
+        n = margin.shape[0]
+        if self._plan is None or self._plan["n"] != n:
+            ptr = self.group_ptr if self.group_ptr is not None else [0, n]
+            self._plan = _hip.lambdarank_plan(ptr, self.num_pair, margin.device)
+        flags = (
+            (_hip.LAMBDARANK_FLAG_NORM if self.normalization else 0)
+            | (_hip.LAMBDARANK_FLAG_SCORE if self.score_normalization else 0)
+            | (_hip.LAMBDARANK_FLAG_EXP_GAIN if self.exp_gain else 0)
+        )
+        kind = torch_ref.LAMBDARANK_KINDS[self.name]
+        return _hip.lambdarank_gradients(self._plan, margin, y, weight, kind, flags)
+
     def _pair_weight(self, y, margin, i, j, g_start, g_end):
         return torch.ones_like(y[i])
 
     def gradients(self, margin, y, weight=None):
+        if self.pair_method == "topk":
+            return self._topk_gradients(margin, y, weight)
         n = margin.shape[0]
         device = margin.device
         grad = torch.zeros_like(margin)

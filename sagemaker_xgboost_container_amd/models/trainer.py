@@ -41,6 +41,8 @@ _TRAIN_PARAM_KEYS = {
     "one_drop", "skip_drop", "rate_drop", "sample_type", "normalize_type", "lambda_bias",
     "huber_slope", "dsplit", "prob_buffer_row", "quantile_alpha",
     "max_cat_to_onehot", "max_cat_threshold",
+    "lambdarank_pair_method", "lambdarank_num_pair_per_sample", "lambdarank_normalization",
+    "lambdarank_score_normalization", "ndcg_exp_gain",
 }
 
 

@@ -210,6 +210,144 @@ def leaf_quantiles(pos, resid, n_leaves, alpha, weight=None, *, weight_max=None,
     return out
 
 
+LAMBDARANK_CAP = int(_K.lambdarank_cap())
+LAMBDARANK_FLAG_NORM, LAMBDARANK_FLAG_SCORE, LAMBDARANK_FLAG_EXP_GAIN = 1, 2, 4
+
+
+def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None):
+    """Work tables of the top-k LambdaRank gradient (csrc/smxgb_rank.hip)
+    for fixed query groups, built once on the host.
+
+    group_ptr: (G+1,) boundaries rising from 0 to n. Runs of consecutive
+    groups become tiles of at most `tile_docs` documents (default and upper
+    limit: LAMBDARANK_CAP) and 256 groups; a group larger than
+    LAMBDARANK_CAP is served by the stream kernels. The result does not
+    depend on the packing, which is what `tile_docs` is there to show."""
+    cap = LAMBDARANK_CAP
+    tile_docs = cap if tile_docs is None else int(tile_docs)
+    k = int(k)
+    if not (1 <= k <= torch_ref.LAMBDARANK_MAX_K):
+        raise ValueError(
+            f"lambdarank_num_pair_per_sample must be in [1, {torch_ref.LAMBDARANK_MAX_K}]"
+        )
+    ptr = (group_ptr.detach().cpu().numpy() if isinstance(group_ptr, torch.Tensor)
+           else np.asarray(group_ptr)).astype(np.int64)
+    if ptr.ndim != 1 or ptr.size < 2 or ptr[0] != 0 or (np.diff(ptr) < 0).any():
+        raise ValueError("group_ptr must rise from 0 to the row count")
+    n = int(ptr[-1])
+    if not (1 <= n < 2**31):
+        raise ValueError("row count must be in [1, 2^31)")
+    sizes = np.diff(ptr)
+    if not (sizes[sizes <= cap].max(initial=1) <= tile_docs <= cap):
+        raise ValueError(f"tile_docs must hold the largest tiled group and be at most {cap}")
+    max_groups = int(_K.lambdarank_max_groups())
+    tiles, stream = [], []
+    first, docs = 0, 0
+    for g, m in enumerate(sizes.tolist()):
+        if m > cap or docs + m > tile_docs or g - first >= max_groups:
+            if g > first:
+                tiles.append((first, g - first))
+            first, docs = g, 0
+        if m > cap:
+            stream.append((int(ptr[g]), m))
+            first = g + 1
+        else:
+            docs += m
+    if len(sizes) > first:
+        tiles.append((first, len(sizes) - first))
+    dev = torch.device(device)
+    kk = min(k, cap)
+    disc = 1.0 / np.log2(np.arange(kk, dtype=np.float64) + 2.0)
+    chunk = int(_K.lambdarank_stream_chunk())
+    max_chunks = max([-(-m // chunk) for _, m in stream], default=0)
+    part_words = max([-(-m // chunk) * min(k, m) * 2 for _, m in stream], default=0)
+    return {
+        "n": n,
+        "k": k,
+        "group_ptr": torch.from_numpy(ptr.astype(np.int32)).to(dev),
+        "tiles": torch.tensor(tiles, dtype=torch.int32).reshape(-1, 2).to(dev),
+        "n_tiles": len(tiles),
+        "stream": stream,
+        "disc_prefix": torch.from_numpy(np.concatenate([[0.0], np.cumsum(disc)])).to(dev),
+        # float64 (g, h, half-lambda) per sorted position; every call
+        # overwrites what it reads
+        "scratch": torch.empty(n * 3, dtype=torch.float64, device=dev),
+        "part": torch.empty(part_words, dtype=torch.float64, device=dev),
+        "psum": torch.empty(max_chunks, dtype=torch.float64, device=dev),
+        "fac": torch.empty(1, dtype=torch.float64, device=dev),
+        "chunk_h": torch.empty(max_chunks, dtype=torch.int32, device=dev),
+        "chunk_S": torch.empty(max_chunks, dtype=torch.float64, device=dev),
+        "pmax_rows": len(tiles) + len(stream) * int(_K.lambdarank_finish_grid()),
+    }
+
+
+def _lambdarank_stream_tables(plan, s, lab, kind, flags):
+    """Tables by position of one group larger than a tile. torch sorts and
+    gathers (no readback); the rank:map prefix tables come from the
+    fixed-order scan kernels, since a library float scan may associate
+    differently from run to run; the pairs run in the stream kernels. What
+    is left to torch in rank:ndcg is elementwise, a sort, and one sum over
+    at most 4096 contiguous values (a fixed reduction tree for a given
+    size)."""
+    dev = s.device
+    m = s.numel()
+    order = torch.sort(-(s + 0.0), stable=True).indices  # descending, ties by row
+    ss = s[order].contiguous()
+    ll = lab[order].contiguous()
+    hits = torch.empty(0, dtype=torch.int32, device=dev)
+    S = torch.empty(0, dtype=torch.float64, device=dev)
+    grp = torch.zeros(1, dtype=torch.float64, device=dev)
+    if kind == 2:
+        hits = torch.empty(m, dtype=torch.int32, device=dev)
+        S = torch.empty(m, dtype=torch.float64, device=dev)
+        _K.lambdarank_map_tables(ll, plan["chunk_h"], plan["chunk_S"], hits, S, grp)
+    elif kind == 1:
+        K = min(plan["k"], m)
+        top = torch.sort(ll, descending=True).values[:K].to(torch.float64)
+        gains = torch.exp2(top) - 1.0 if flags & LAMBDARANK_FLAG_EXP_GAIN else top
+        S = 1.0 / torch.log2(torch.arange(2, m + 2, dtype=torch.float64, device=dev))  # disc(p)
+        idcg = (gains * S[:K]).sum().reshape(1)
+        grp = torch.where(idcg > 0, 1.0 / idcg, torch.zeros_like(idcg))
+    return order, ss, ll, hits, S, grp.contiguous()
+
+
+def lambdarank_gradients(plan, margin, y, weight, kind, flags):
+    """Top-k LambdaRank gradients on the device; the rule and the float64
+    reference are torch_ref.lambdarank_gradients. kind: 0 rank:pairwise,
+    1 rank:ndcg, 2 rank:map; flags: LAMBDARANK_FLAG_* bits. Returns the
+    packed (n, 2) float32 gh with `_smxgb_absmax` attached. Nothing is read
+    back, the result is the same bit for bit from call to call and does
+    not depend on the plan's tile packing. Labels are validated by the
+    caller (torch_ref.check_lambdarank_labels). A NaN margin, an error by
+    the rule, cannot raise here without a readback: it turns both entries
+    of `_smxgb_absmax` into NaN, and the gradients of its group are then
+    meaningless."""
+    n = plan["n"]
+    if not margin.is_cuda or margin.dim() != 1 or margin.numel() != n or y.numel() != n:
+        raise ValueError("margin and y must be 1-d ROCm device tensors with the plan's row count")
+    dev = margin.device
+    margin = margin.to(torch.float32).contiguous()
+    y = y.to(torch.float32).contiguous()
+    w = (weight.to(torch.float32).contiguous() if (weight is not None and weight.numel())
+         else torch.empty(0, dtype=torch.float32, device=dev))
+    gh = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    pmax = torch.zeros((plan["pmax_rows"], 2), dtype=torch.float32, device=dev)
+    kind, flags, k = int(kind), int(flags), plan["k"]
+    if plan["n_tiles"]:
+        _K.lambdarank_tile(margin, y, w, plan["group_ptr"], plan["tiles"], plan["disc_prefix"],
+                           k, kind, flags, plan["scratch"], gh, pmax)
+    rows = plan["n_tiles"]
+    step = int(_K.lambdarank_finish_grid())
+    for gs, m in plan["stream"]:
+        order, ss, ll, hits, S, grp = _lambdarank_stream_tables(
+            plan, margin[gs:gs + m], y[gs:gs + m], kind, flags)
+        _K.lambdarank_stream(ss, ll, hits, S, grp, order, w, gs, k, kind, flags, plan["scratch"],
+                             plan["part"], plan["psum"], plan["fac"], gh, pmax[rows:rows + step])
+        rows += step
+    gh._smxgb_absmax = pmax.amax(dim=0).contiguous()
+    return gh
+
+
 def _padded_words(pairs):
     """LDS u64 words for `pairs` histogram slots incl. bank-skew padding."""
     return (pairs + (pairs >> 3) + 1) * 2
