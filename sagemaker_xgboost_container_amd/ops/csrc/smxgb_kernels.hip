@@ -2539,25 +2539,28 @@ void leaf_update_traverse(torch::Tensor bins, torch::Tensor splits, torch::Tenso
   }
 }
 
-void grow_make_root(torch::Tensor nodes, torch::Tensor hist_prefix, torch::Tensor part_prefix,
-                    torch::Tensor work, int64_t cap, int64_t rows_per_block, int64_t max_blocks) {
-  hipLaunchKernelGGL(make_root_kernel, dim3(1), dim3(1), 0, current_stream(),
-                     (LevelNode*)nodes.data_ptr<int>(), hist_prefix.data_ptr<int>(),
-                     part_prefix.data_ptr<int>(), (LevelWork*)work.data_ptr<int>(), (int)cap,
-                     (int)rows_per_block, (int)max_blocks);
+// The depthwise grower's kernel families have one launch site each (the
+// launch_* helpers below): the level loop in grow_tree_enqueue and the
+// stand-alone grow_* / find_splits bindings both go through it.
+static void launch_make_level(hipStream_t stream, const LevelNode* cur, const float* splits,
+                              const int* counts, const float* node_gh, LevelNode* nxt,
+                              float* nxt_gh, int* hist_prefix, int* part_prefix, LevelWork* work,
+                              int k, int rows_per_block, int max_blocks, int filtered) {
+  hipLaunchKernelGGL(make_level_kernel, dim3(1), dim3(GROW_MAX_SLOTS), 0, stream, cur, splits,
+                     counts, node_gh, nxt, nxt_gh, hist_prefix, part_prefix, work, k,
+                     rows_per_block, max_blocks, filtered);
 }
 
 void grow_make_level(torch::Tensor cur, torch::Tensor splits, torch::Tensor counts,
                      torch::Tensor node_gh, torch::Tensor nxt, torch::Tensor nxt_gh,
                      torch::Tensor hist_prefix, torch::Tensor part_prefix, torch::Tensor work,
                      int64_t k, int64_t rows_per_block, int64_t max_blocks, int64_t filtered) {
-  hipLaunchKernelGGL(make_level_kernel, dim3(1), dim3(GROW_MAX_SLOTS), 0, current_stream(),
-                     (const LevelNode*)cur.data_ptr<int>(), splits.data_ptr<float>(),
-                     counts.data_ptr<int>(), node_gh.data_ptr<float>(),
-                     (LevelNode*)nxt.data_ptr<int>(), nxt_gh.data_ptr<float>(),
-                     hist_prefix.data_ptr<int>(), part_prefix.data_ptr<int>(),
-                     (LevelWork*)work.data_ptr<int>(), (int)k, (int)rows_per_block,
-                     (int)max_blocks, (int)filtered);
+  launch_make_level(current_stream(), (const LevelNode*)cur.data_ptr<int>(),
+                    splits.data_ptr<float>(), counts.data_ptr<int>(), node_gh.data_ptr<float>(),
+                    (LevelNode*)nxt.data_ptr<int>(), nxt_gh.data_ptr<float>(),
+                    hist_prefix.data_ptr<int>(), part_prefix.data_ptr<int>(),
+                    (LevelWork*)work.data_ptr<int>(), (int)k, (int)rows_per_block,
+                    (int)max_blocks, (int)filtered);
 }
 
 // dispatch helper: BLOCK is a compile-time launch bound (256 grouped-slab,
@@ -2627,6 +2630,17 @@ static void launch_hist_device(int grid, int hist_block, size_t lds_bytes, hipSt
   }
 }
 
+// launch_hist_device with the bin type dispatched (u8, else int16)
+template <typename... Rest>
+static void launch_hist_level(bool u8, int grid, int hist_block, size_t lds_bytes,
+                              hipStream_t stream, const void* bins_c, Rest... rest) {
+  if (u8) {
+    launch_hist_device(grid, hist_block, lds_bytes, stream, (const unsigned char*)bins_c, rest...);
+  } else {
+    launch_hist_device(grid, hist_block, lds_bytes, stream, (const short*)bins_c, rest...);
+  }
+}
+
 void grow_hist_level(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor nodes,
                      torch::Tensor hist_prefix, torch::Tensor work, torch::Tensor acc,
                      int64_t k, int64_t nfeat, int64_t stride, int64_t n_groups,
@@ -2646,43 +2660,50 @@ void grow_hist_level(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor nod
                 "grow_hist_level: parent split records must be a contiguous float32 [k/2, 6]");
     par_ptr = par_splits.data_ptr<float>();
   }
-  if (bins_c.scalar_type() == torch::kUInt8) {
-    launch_hist_device<unsigned char>(
-        (int)grid, (int)hist_block, lds_bytes, stream, bins_c.data_ptr<unsigned char>(),
-        (const float2*)gh_c.data_ptr<float>(), (const LevelNode*)nodes.data_ptr<int>(),
-        hist_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
-        (unsigned long long*)acc.data_ptr<int64_t>(), (int)k, (int)nfeat, (int)stride,
-        (int)n_groups, (int)feats_per_group, gh_max.data_ptr<float>(), (int)rows_per_block,
-        (int)slot_lo, (int)slot_hi, par_ptr, (int)missing_bin, predicate_only != 0);
-  } else {
-    launch_hist_device<short>(
-        (int)grid, (int)hist_block, lds_bytes, stream, bins_c.data_ptr<short>(),
-        (const float2*)gh_c.data_ptr<float>(), (const LevelNode*)nodes.data_ptr<int>(),
-        hist_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
-        (unsigned long long*)acc.data_ptr<int64_t>(), (int)k, (int)nfeat, (int)stride,
-        (int)n_groups, (int)feats_per_group, gh_max.data_ptr<float>(), (int)rows_per_block,
-        (int)slot_lo, (int)slot_hi, par_ptr, (int)missing_bin, predicate_only != 0);
-  }
+  launch_hist_level(
+      bins_c.scalar_type() == torch::kUInt8, (int)grid, (int)hist_block, lds_bytes, stream,
+      bins_c.data_ptr(), (const float2*)gh_c.data_ptr<float>(),
+      (const LevelNode*)nodes.data_ptr<int>(), hist_prefix.data_ptr<int>(),
+      (const LevelWork*)work.data_ptr<int>(), (unsigned long long*)acc.data_ptr<int64_t>(),
+      (int)k, (int)nfeat, (int)stride, (int)n_groups, (int)feats_per_group,
+      gh_max.data_ptr<float>(), (int)rows_per_block, (int)slot_lo, (int)slot_hi, par_ptr,
+      (int)missing_bin, predicate_only != 0);
+}
+
+// Fixed point -> float32 for the slots built from rows; with the parent
+// level's histograms given, every other slot as parent minus sibling.
+static void launch_convert_derive(hipStream_t stream, const unsigned long long* acc,
+                                  float* level_hist, const float* parent_hist,
+                                  const LevelNode* nodes, int k, long long slots2,
+                                  const float* gh_max) {
+  const long long total = (long long)k * slots2;
+  const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 2048);
+  hipLaunchKernelGGL(convert_level_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0, stream,
+                     acc, level_hist, nodes, k, slots2, gh_max);
+  if (parent_hist != nullptr)
+    hipLaunchKernelGGL(derive_level_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0, stream,
+                       level_hist, parent_hist, nodes, k, slots2);
 }
 
 void grow_convert_level(torch::Tensor acc, torch::Tensor hist_f32, torch::Tensor nodes,
                         int64_t k, int64_t slots2, torch::Tensor gh_max) {
-  const long long total = (long long)k * slots2;
-  const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 2048);
-  hipLaunchKernelGGL(convert_level_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0,
-                     current_stream(), (const unsigned long long*)acc.data_ptr<int64_t>(),
-                     hist_f32.data_ptr<float>(), (const LevelNode*)nodes.data_ptr<int>(), (int)k,
-                     slots2, gh_max.data_ptr<float>());
+  launch_convert_derive(current_stream(), (const unsigned long long*)acc.data_ptr<int64_t>(),
+                        hist_f32.data_ptr<float>(), nullptr,
+                        (const LevelNode*)nodes.data_ptr<int>(), (int)k, slots2,
+                        gh_max.data_ptr<float>());
 }
 
-void grow_derive_level(torch::Tensor level_hist, torch::Tensor parent_hist, torch::Tensor nodes,
-                       int64_t k, int64_t slots2) {
-  const long long total = (long long)k * slots2;
-  const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 2048);
-  hipLaunchKernelGGL(derive_level_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0,
-                     current_stream(), level_hist.data_ptr<float>(),
-                     parent_hist.data_ptr<float>(), (const LevelNode*)nodes.data_ptr<int>(),
-                     (int)k, slots2);
+static void launch_find_splits(hipStream_t stream, const float* hist, const float2* parent,
+                               const int* nbins, const unsigned char* feat_mask,
+                               const signed char* monotone, SplitCand* cands, float* out, int k,
+                               int f, int stride, int has_missing, int mask_per_node,
+                               float reg_lambda, float reg_alpha, float gamma_,
+                               float min_child_weight) {
+  hipLaunchKernelGGL(split_scan_kernel, dim3(k * f), dim3(SPLIT_BLOCK), 0, stream, hist, parent,
+                     nbins, feat_mask, monotone, cands, k, f, stride, has_missing, mask_per_node,
+                     reg_lambda, reg_alpha, gamma_, min_child_weight);
+  hipLaunchKernelGGL(split_reduce_kernel, dim3(k), dim3(SPLIT_BLOCK), 0, stream,
+                     (const SplitCand*)cands, out, k, f);
 }
 
 // Which kernel partitions a level (SMXGB_PARTITION, pushed in by ops/hip.py
@@ -2717,38 +2738,49 @@ int64_t partition_tile(int64_t nfeat, int64_t u8, int64_t copy_payload) {
   return staged_partition_tile((int)nfeat, u8 != 0, (int)copy_payload);
 }
 
-static bool launch_part_staged(int grid, hipStream_t stream, const unsigned char* src_bins,
-                               const float2* src_gh, const int* src_rows,
-                               unsigned char* dst_bins, float2* dst_gh, int* dst_rows,
-                               const LevelNode* nodes, const int* part_prefix,
-                               const LevelWork* work, const float* split_packed, int* counters,
-                               int k, int nfeat, int missing_bin, int copy_payload,
-                               int copy_rows) {
-  const int tile = staged_partition_tile(nfeat, true, copy_payload);
-  if (tile == 0) return false;
+// Partition one level: the staged kernel where staged_partition_tile() gives
+// a tile, else the classic kernel of the bin type.
+static void launch_partition_level(bool u8, int grid, hipStream_t stream, const void* src_bins,
+                                   const float2* src_gh, const int* src_rows, void* dst_bins,
+                                   float2* dst_gh, int* dst_rows, const LevelNode* nodes,
+                                   const int* part_prefix, const LevelWork* work,
+                                   const float* split_packed, int* counters, int k, int nfeat,
+                                   int missing_bin, int copy_payload, int copy_rows) {
+  const int tile = staged_partition_tile(nfeat, u8, copy_payload);
 #define SMXGB_LAUNCH_STAGED(BLOCK, R)                                                          \
   do {                                                                                         \
+    const unsigned char* sb = (const unsigned char*)src_bins;                                  \
+    unsigned char* db = (unsigned char*)dst_bins;                                              \
     if (copy_rows) {                                                                           \
       hipLaunchKernelGGL((partition_device_staged_kernel<BLOCK, R, true>), dim3(grid),         \
-                         dim3(BLOCK), 0, stream, src_bins, src_gh, src_rows, dst_bins, dst_gh, \
-                         dst_rows, nodes, part_prefix, work, split_packed, counters, k, nfeat, \
+                         dim3(BLOCK), 0, stream, sb, src_gh, src_rows, db, dst_gh, dst_rows,   \
+                         nodes, part_prefix, work, split_packed, counters, k, nfeat,           \
                          missing_bin);                                                         \
     } else {                                                                                   \
       hipLaunchKernelGGL((partition_device_staged_kernel<BLOCK, R, false>), dim3(grid),        \
-                         dim3(BLOCK), 0, stream, src_bins, src_gh, src_rows, dst_bins, dst_gh, \
-                         dst_rows, nodes, part_prefix, work, split_packed, counters, k, nfeat, \
+                         dim3(BLOCK), 0, stream, sb, src_gh, src_rows, db, dst_gh, dst_rows,   \
+                         nodes, part_prefix, work, split_packed, counters, k, nfeat,           \
                          missing_bin);                                                         \
     }                                                                                          \
   } while (0)
+#define SMXGB_LAUNCH_CLASSIC(BinT)                                                             \
+  hipLaunchKernelGGL(partition_device_kernel<BinT>, dim3(grid), dim3(HIST_BLOCK), 0, stream,   \
+                     (const BinT*)src_bins, src_gh, src_rows, (BinT*)dst_bins, dst_gh,         \
+                     dst_rows, nodes, part_prefix, work, split_packed, counters, k, nfeat,     \
+                     missing_bin, copy_payload, copy_rows)
   if (tile == 2048) {
     SMXGB_LAUNCH_STAGED(512, 32);
   } else if (tile == 1024) {
     SMXGB_LAUNCH_STAGED(256, 32);
-  } else {
+  } else if (tile != 0) {
     SMXGB_LAUNCH_STAGED(256, 16);
+  } else if (u8) {
+    SMXGB_LAUNCH_CLASSIC(unsigned char);
+  } else {
+    SMXGB_LAUNCH_CLASSIC(short);
   }
 #undef SMXGB_LAUNCH_STAGED
-  return true;
+#undef SMXGB_LAUNCH_CLASSIC
 }
 
 void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::Tensor src_rows,
@@ -2757,34 +2789,14 @@ void grow_partition_level(torch::Tensor src_bins, torch::Tensor src_gh, torch::T
                           torch::Tensor split_packed, torch::Tensor counters, int64_t k,
                           int64_t nfeat, int64_t missing_bin, int64_t grid,
                           int64_t copy_payload, int64_t copy_rows) {
-  auto stream = current_stream();
-  if (src_bins.scalar_type() == torch::kUInt8) {
-    if (launch_part_staged((int)grid, stream, src_bins.data_ptr<unsigned char>(),
-                           (const float2*)src_gh.data_ptr<float>(), src_rows.data_ptr<int>(),
-                           dst_bins.data_ptr<unsigned char>(), (float2*)dst_gh.data_ptr<float>(),
-                           dst_rows.data_ptr<int>(), (const LevelNode*)nodes.data_ptr<int>(),
-                           part_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
-                           split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)k,
-                           (int)nfeat, (int)missing_bin, (int)copy_payload, (int)copy_rows))
-      return;
-    hipLaunchKernelGGL(partition_device_kernel<unsigned char>, dim3((int)grid), dim3(HIST_BLOCK),
-                       0, stream, src_bins.data_ptr<unsigned char>(),
-                       (const float2*)src_gh.data_ptr<float>(), src_rows.data_ptr<int>(),
-                       dst_bins.data_ptr<unsigned char>(), (float2*)dst_gh.data_ptr<float>(),
-                       dst_rows.data_ptr<int>(), (const LevelNode*)nodes.data_ptr<int>(),
-                       part_prefix.data_ptr<int>(), (const LevelWork*)work.data_ptr<int>(),
-                       split_packed.data_ptr<float>(), counters.data_ptr<int>(), (int)k,
-                       (int)nfeat, (int)missing_bin, (int)copy_payload, (int)copy_rows);
-  } else {
-    hipLaunchKernelGGL(partition_device_kernel<short>, dim3((int)grid), dim3(HIST_BLOCK), 0,
-                       stream, src_bins.data_ptr<short>(), (const float2*)src_gh.data_ptr<float>(),
-                       src_rows.data_ptr<int>(), dst_bins.data_ptr<short>(),
-                       (float2*)dst_gh.data_ptr<float>(), dst_rows.data_ptr<int>(),
-                       (const LevelNode*)nodes.data_ptr<int>(), part_prefix.data_ptr<int>(),
-                       (const LevelWork*)work.data_ptr<int>(), split_packed.data_ptr<float>(),
-                       counters.data_ptr<int>(), (int)k, (int)nfeat, (int)missing_bin,
-                       (int)copy_payload, (int)copy_rows);
-  }
+  launch_partition_level(
+      src_bins.scalar_type() == torch::kUInt8, (int)grid, current_stream(), src_bins.data_ptr(),
+      (const float2*)src_gh.data_ptr<float>(), src_rows.data_ptr<int>(), dst_bins.data_ptr(),
+      (float2*)dst_gh.data_ptr<float>(), dst_rows.data_ptr<int>(),
+      (const LevelNode*)nodes.data_ptr<int>(), part_prefix.data_ptr<int>(),
+      (const LevelWork*)work.data_ptr<int>(), split_packed.data_ptr<float>(),
+      counters.data_ptr<int>(), (int)k, (int)nfeat, (int)missing_bin, (int)copy_payload,
+      (int)copy_rows);
 }
 
 // One level's interaction-constraint step on its own (the whole-tree
@@ -2811,8 +2823,13 @@ void grow_node_mask(torch::Tensor par_nodes, torch::Tensor par_splits, torch::Te
 }
 
 // Whole-tree enqueue: the entire depthwise grow issued from C++ in one
-// Python call (single-process path; the distributed path keeps the Python
-// per-level loop so torch.distributed can enqueue the allreduce).
+// Python call; the only place that walks the levels. `hist_hook` is None or
+// a Python callable that takes over one step: with a hook, level d's
+// histogram launch is replaced by hist_hook(d, src, filtered) on zeroed
+// acc[:k], where src names the buffers the level reads (-1 the init set,
+// else the parity) and filtered is 1 on the filtered deepest level. The
+// distributed path builds and allreduces `acc` there. An exception the hook
+// raises leaves this function as that Python exception.
 void grow_tree_enqueue(
     torch::Tensor init_bins, torch::Tensor init_gh, torch::Tensor init_rows,
     torch::Tensor bins0, torch::Tensor gh0, torch::Tensor rows0,
@@ -2826,7 +2843,8 @@ void grow_tree_enqueue(
     int64_t feats_per_group, int64_t lds_words, int64_t has_missing, int64_t missing_bin,
     int64_t rows_per_block, int64_t max_blocks, int64_t hist_grid, int64_t part_grid,
     double reg_lambda, double reg_alpha, double gamma_, double min_child_weight,
-    int64_t hist_block, int64_t skip_last_partition, int64_t filter_deepest) {
+    int64_t hist_block, int64_t skip_last_partition, int64_t filter_deepest,
+    pybind11::object hist_hook) {
   CHECK_GPU(init_bins);
   auto stream = current_stream();
   // Margins updated by traversal (skip_last_partition): nothing reads row
@@ -2881,13 +2899,12 @@ void grow_tree_enqueue(
     } else {
       const int pk = k >> 1;
       const int pbase = pk - 1;
-      hipLaunchKernelGGL(make_level_kernel, dim3(1), dim3(GROW_MAX_SLOTS), 0, stream,
-                         (const LevelNode*)nodes.data_ptr<int>() + pbase,
-                         splits.data_ptr<float>() + (long long)pbase * 6,
-                         counts.data_ptr<int>() + (long long)pbase * 2,
-                         node_gh.data_ptr<float>() + (long long)pbase * 2, nodes_d, gh_d, hp_d,
-                         pp_d, work_d, pk, (int)rows_per_block, (int)max_blocks,
-                         filtered ? 1 : 0);
+      launch_make_level(stream, (const LevelNode*)nodes.data_ptr<int>() + pbase,
+                        splits.data_ptr<float>() + (long long)pbase * 6,
+                        counts.data_ptr<int>() + (long long)pbase * 2,
+                        node_gh.data_ptr<float>() + (long long)pbase * 2, nodes_d, gh_d, hp_d,
+                        pp_d, work_d, pk, (int)rows_per_block, (int)max_blocks,
+                        filtered ? 1 : 0);
     }
 
     // a filtered level reads what the level above it read
@@ -2905,34 +2922,19 @@ void grow_tree_enqueue(
     int* dst_rows = dpar ? rows1.data_ptr<int>() : rows0.data_ptr<int>();
 
     hipMemsetAsync(acc.data_ptr<int64_t>(), 0, sizeof(int64_t) * (size_t)k * slots2, stream);
-    if (u8) {
-      launch_hist_device<unsigned char>(
-          (int)hist_grid, (int)hist_block, lds_bytes, stream, (const unsigned char*)src_bins,
-          src_gh, nodes_d, hp_d, work_d, (unsigned long long*)acc.data_ptr<int64_t>(), k,
-          (int)nfeat, (int)stride, (int)n_groups, (int)feats_per_group,
-          gh_max.data_ptr<float>(), (int)rows_per_block, 0, 1 << 30, par_splits,
-          (int)missing_bin, filter_deepest == 2);
+    unsigned long long* acc_ptr = (unsigned long long*)acc.data_ptr<int64_t>();
+    if (hist_hook.is_none()) {
+      launch_hist_level(u8, (int)hist_grid, (int)hist_block, lds_bytes, stream, src_bins, src_gh,
+                        nodes_d, hp_d, work_d, acc_ptr, k, (int)nfeat, (int)stride, (int)n_groups,
+                        (int)feats_per_group, gh_max.data_ptr<float>(), (int)rows_per_block, 0,
+                        1 << 30, par_splits, (int)missing_bin, filter_deepest == 2);
     } else {
-      launch_hist_device<short>(
-          (int)hist_grid, (int)hist_block, lds_bytes, stream, (const short*)src_bins, src_gh,
-          nodes_d, hp_d, work_d, (unsigned long long*)acc.data_ptr<int64_t>(), k, (int)nfeat,
-          (int)stride, (int)n_groups, (int)feats_per_group, gh_max.data_ptr<float>(),
-          (int)rows_per_block, 0, 1 << 30, par_splits, (int)missing_bin, filter_deepest == 2);
+      hist_hook(d, level0 ? -1 : (int)par, filtered ? 1 : 0);
     }
-
-    {
-      const long long total = (long long)k * slots2;
-      const int grid = (int)std::min<long long>((total + HIST_BLOCK - 1) / HIST_BLOCK, 2048);
-      hipLaunchKernelGGL(convert_level_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0,
-                         stream, (const unsigned long long*)acc.data_ptr<int64_t>(), hist_d,
-                         nodes_d, k, slots2, gh_max.data_ptr<float>());
-      if (d > 0) {
-        const int pbase = (k >> 1) - 1;
-        hipLaunchKernelGGL(derive_level_kernel, dim3(std::max(grid, 1)), dim3(HIST_BLOCK), 0,
-                           stream, hist_d, hist_f32.data_ptr<float>() + (long long)pbase * slots2,
-                           nodes_d, k, slots2);
-      }
-    }
+    launch_convert_derive(
+        stream, acc_ptr, hist_d,
+        d > 0 ? hist_f32.data_ptr<float>() + (long long)((k >> 1) - 1) * slots2 : nullptr,
+        nodes_d, k, slots2, gh_max.data_ptr<float>());
 
     const unsigned char* mask_ptr = mask_base ? mask_base + (long long)d * mask_row : nullptr;
     int mask_per_node = 0;
@@ -2949,13 +2951,10 @@ void grow_tree_enqueue(
       mask_ptr = node_mask.data_ptr<unsigned char>();
       mask_per_node = 1;
     }
-    hipLaunchKernelGGL(split_scan_kernel, dim3(k * (int)nfeat), dim3(SPLIT_BLOCK), 0, stream,
-                       hist_d, (const float2*)gh_d, nbins.data_ptr<int>(), mask_ptr, mono_ptr,
-                       (SplitCand*)cands.data_ptr<float>(), k, (int)nfeat, (int)stride,
-                       (int)has_missing, mask_per_node, (float)reg_lambda, (float)reg_alpha, (float)gamma_,
-                       (float)min_child_weight);
-    hipLaunchKernelGGL(split_reduce_kernel, dim3(k), dim3(SPLIT_BLOCK), 0, stream,
-                       (const SplitCand*)cands.data_ptr<float>(), splits_d, k, (int)nfeat);
+    launch_find_splits(stream, hist_d, (const float2*)gh_d, nbins.data_ptr<int>(), mask_ptr,
+                       mono_ptr, (SplitCand*)cands.data_ptr<float>(), splits_d, k, (int)nfeat,
+                       (int)stride, (int)has_missing, mask_per_node, (float)reg_lambda,
+                       (float)reg_alpha, (float)gamma_, (float)min_child_weight);
 
     const int copy_payload = d < (int)D - 1 ? 1 : 0;  // last level: rows+counts only
     // margins updated by traversal: nothing consumes the deepest level's
@@ -2963,22 +2962,9 @@ void grow_tree_enqueue(
     if (!copy_payload && skip_last_partition) continue;
     // ... and with the filtered deepest histogram, neither is level D-2
     if (filter_last && d == (int)D - 2) continue;
-    if (u8) {
-      if (!launch_part_staged((int)part_grid, stream, (const unsigned char*)src_bins, src_gh,
-                              src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d,
-                              pp_d, work_d, splits_d, counts_d, k, (int)nfeat,
-                              (int)missing_bin, copy_payload, copy_rows))
-        hipLaunchKernelGGL(partition_device_kernel<unsigned char>, dim3((int)part_grid),
-                           dim3(HIST_BLOCK), 0, stream, (const unsigned char*)src_bins, src_gh,
-                           src_rows, (unsigned char*)dst_bins, dst_gh, dst_rows, nodes_d, pp_d,
-                           work_d, splits_d, counts_d, k, (int)nfeat, (int)missing_bin,
-                           copy_payload, copy_rows);
-    } else {
-      hipLaunchKernelGGL(partition_device_kernel<short>, dim3((int)part_grid), dim3(HIST_BLOCK),
-                         0, stream, (const short*)src_bins, src_gh, src_rows, (short*)dst_bins,
-                         dst_gh, dst_rows, nodes_d, pp_d, work_d, splits_d, counts_d, k,
-                         (int)nfeat, (int)missing_bin, copy_payload, copy_rows);
-    }
+    launch_partition_level(u8, (int)part_grid, stream, src_bins, src_gh, src_rows, dst_bins,
+                           dst_gh, dst_rows, nodes_d, pp_d, work_d, splits_d, counts_d, k,
+                           (int)nfeat, (int)missing_bin, copy_payload, copy_rows);
   }
 }
 
@@ -3017,20 +3003,15 @@ void find_splits(torch::Tensor hist, torch::Tensor parent, torch::Tensor nbins,
                  int64_t mask_per_node, double reg_lambda, double reg_alpha, double gamma_,
                  double min_child_weight) {
   CHECK_GPU(hist);
-  auto stream = current_stream();
   const unsigned char* mask_ptr =
       feat_mask.numel() ? feat_mask.data_ptr<unsigned char>() : nullptr;
   const signed char* mono_ptr =
       monotone.numel() ? (const signed char*)monotone.data_ptr<int8_t>() : nullptr;
-  hipLaunchKernelGGL(split_scan_kernel, dim3((int)(k * f)), dim3(SPLIT_BLOCK), 0, stream,
-                     hist.data_ptr<float>(), (const float2*)parent.data_ptr<float>(),
-                     nbins.data_ptr<int>(), mask_ptr, mono_ptr,
-                     (SplitCand*)cands.data_ptr<float>(), (int)k, (int)f, (int)stride,
-                     (int)has_missing, (int)mask_per_node, (float)reg_lambda, (float)reg_alpha,
-                     (float)gamma_, (float)min_child_weight);
-  hipLaunchKernelGGL(split_reduce_kernel, dim3((int)k), dim3(SPLIT_BLOCK), 0, stream,
-                     (const SplitCand*)cands.data_ptr<float>(), out.data_ptr<float>(), (int)k,
-                     (int)f);
+  launch_find_splits(current_stream(), hist.data_ptr<float>(),
+                     (const float2*)parent.data_ptr<float>(), nbins.data_ptr<int>(), mask_ptr,
+                     mono_ptr, (SplitCand*)cands.data_ptr<float>(), out.data_ptr<float>(), (int)k,
+                     (int)f, (int)stride, (int)has_missing, (int)mask_per_node, (float)reg_lambda,
+                     (float)reg_alpha, (float)gamma_, (float)min_child_weight);
 }
 
 // find_splits() for a matrix with categorical columns, on one stream:
@@ -3131,11 +3112,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pred_leaf_cat", &pred_leaf_cat, "leaf index per (row, tree) with categorical nodes");
   m.def("hist_build_compact", &hist_build_compact, "streaming histogram over compact row buffers");
   m.def("hist_convert_dev", &hist_convert_dev, "fixed-point -> f32 convert with device-resident scale");
-  m.def("grow_make_root", &grow_make_root);
   m.def("grow_make_level", &grow_make_level);
   m.def("grow_hist_level", &grow_hist_level);
   m.def("grow_convert_level", &grow_convert_level);
-  m.def("grow_derive_level", &grow_derive_level);
   m.def("grow_partition_level", &grow_partition_level);
   m.def("set_partition_mode", &set_partition_mode,
         "0 classic, 1 staged, 512/1024/2048 staged at that tile");

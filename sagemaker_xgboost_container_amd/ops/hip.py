@@ -1512,9 +1512,11 @@ class DeviceGrower:
         if not hasattr(qm, "_nbins_i32"):
             qm._nbins_i32 = qm.nbins.to(torch.int32).contiguous()
 
-    def _enqueue_body(self, gh_init, scale, split_params, rootsum=None, alloc_free=False):
+    def _enqueue_body(self, gh_init, scale, split_params, rootsum=None, alloc_free=False,
+                      hist_hook=None):
         """The tree's full kernel sequence + pinned readback. Pointer-stable
-        given (gh_init, scale) tensors — hipGraph-capturable.
+        given (gh_init, scale) tensors — hipGraph-capturable when `hist_hook`
+        (see _comm_hist_hook) is None.
 
         alloc_free=True (the captured variant) requires `rootsum` staged by
         the caller and performs ZERO allocator calls: capture-time
@@ -1556,6 +1558,7 @@ class DeviceGrower:
             reg_lambda, reg_alpha, gamma, mcw, self.hist_block,
             1 if self.traverse else 0,
             _DEEPEST_HIST_MODES[_DEEPEST_HIST],
+            hist_hook,
         )
         if not hasattr(self, "_pinned"):
             self._pinned = (
@@ -1567,28 +1570,33 @@ class DeviceGrower:
         self._pinned[1].copy_(self.counts, non_blocking=True)
         self._pinned[2].copy_(self.node_gh[0], non_blocking=True)
 
-    def _graph_eligible(self):
+    def _graph_eligible(self, hist_hook=None):
         """hipGraph replay needs stable pointers: full-data state (bins/rows
         alias the matrix; only gh changes round to round — staged) and no
         per-tree feature mask (its contents change every tree) or
-        constraint table."""
+        constraint table. A captured graph cannot call Python either, so
+        never with a histogram hook."""
         st = self.state
         # default OFF: capture/replay of this sequence currently memory-
         # faults on gfx950 (gpurun_out/graph_triage.log); opt in with
         # SMXGB_HIPGRAPH=1 once the faulting node is resolved
         return (
-            _os.environ.get("SMXGB_HIPGRAPH", "0") == "1"
+            hist_hook is None
+            and _os.environ.get("SMXGB_HIPGRAPH", "0") == "1"
             and st._bins_init is self.qm.bins
             and self.mask.numel() == 0
             and self.mono.numel() == 0
             and self.inter_union.numel() == 0
         )
 
-    def grow_enqueue(self, scale, split_params):
+    def grow_enqueue(self, scale, split_params, comm=None):
         """Enqueue the full tree plus the non-blocking heap readback into
         pinned host buffers; returns a torch.cuda.Event to wait on. Lets the
         caller enqueue several independent trees (multiclass / bagging
         rounds) back-to-back so the GPU never idles between them.
+
+        With a communicator the root sum is allreduced here and every
+        level's histograms in the hook handed to the same level loop.
 
         When eligible, the ~45-kernel sequence is captured ONCE into a
         hipGraph and replayed as a single launch per tree (the per-launch
@@ -1598,7 +1606,15 @@ class DeviceGrower:
         """
         st = self.state
         rootsum = getattr(st._gh_init, "_smxgb_rootsum", None)
-        if self._graph_eligible():
+        hist_hook = None
+        if comm is not None:
+            # constrained trees with a communicator stay on the per-level
+            # path (HistGrower._device_fallback_reason)
+            assert self.mask.dim() <= 1 and self.inter_union.numel() == 0 and self.mono.numel() == 0
+            rootsum = rootsum.clone() if rootsum is not None else st._gh_init.to(torch.float64).sum(0)
+            comm.allreduce_(rootsum)
+            hist_hook = self._comm_hist_hook(scale, comm)
+        if self._graph_eligible(hist_hook):
             # root (G, H) must stay BIT-identical with the non-graphed
             # paths: the fused-gradient partial sum (when present) is
             # staged; otherwise the same f64 sum runs EAGERLY here (the
@@ -1662,7 +1678,8 @@ class DeviceGrower:
                 torch.cuda.synchronize()
                 print("[graphdbg] replay ok", file=_sys.stderr, flush=True)
         else:
-            self._enqueue_body(st._gh_init, scale, split_params, rootsum=rootsum)
+            self._enqueue_body(st._gh_init, scale, split_params, rootsum=rootsum,
+                               hist_hook=hist_hook)
         ev = torch.cuda.Event()
         ev.record()
         return ev
@@ -1681,99 +1698,59 @@ class DeviceGrower:
     def grow(self, scale, split_params, comm=None):
         """Enqueue the full tree; returns (splits_np [H,6], counts_np [H,2],
         root_gh_np [2])."""
-        if comm is None:
-            return self.grow_wait(self.grow_enqueue(scale, split_params))
+        return self.grow_wait(self.grow_enqueue(scale, split_params, comm))
 
-        # the distributed loop knows neither per-level masks nor
-        # interaction constraints: constrained trees with a communicator
-        # stay on the per-level path
-        assert self.mask.dim() <= 1 and self.inter_union.numel() == 0 and self.mono.numel() == 0
+    def _comm_hist_hook(self, scale, comm):
+        """The histogram step grow_tree_enqueue hands over when a
+        communicator is present: hook(d, src, filtered) builds level d's
+        fixed-point histograms into the zeroed `acc[:k]` from the buffer set
+        the loop chose (src -1: the init set, else the parity; filtered: the
+        deepest level reading through its parents' splits) and allreduces
+        them before the loop goes on to convert them."""
         st = self.state
         qm = self.qm
         f = qm.num_col
         stride = qm.stride
         missing_bin = stride - 1 if qm.has_missing else -1
-        reg_lambda, reg_alpha, gamma, mcw = split_params
-
-        self.counts.zero_()
-        root_gh = getattr(st._gh_init, "_smxgb_rootsum", None)
-        root_gh = root_gh.clone() if root_gh is not None else st._gh_init.to(torch.float64).sum(0)
-        comm.allreduce_(root_gh)
-        self.node_gh[0] = root_gh.to(torch.float32)
-
-        # traversal needs no row ids; with the filtered deepest histogram
-        # level D-2 is not partitioned either (see grow_tree_enqueue)
-        filter_mode = _DEEPEST_HIST_MODES[_DEEPEST_HIST]
-        filter_last = self.traverse and filter_mode != 0 and self.D >= 2
-        predicate_only = 1 if filter_mode == 2 else 0
-        copy_rows = 0 if self.traverse else 1
+        predicate_only = 1 if _DEEPEST_HIST_MODES[_DEEPEST_HIST] == 2 else 0
         no_splits = torch.empty(0, dtype=torch.float32, device=self.splits.device)
+        # Default ON for real multi-rank groups (the driver's scaling
+        # run): correctness is proven bit-identical under gloo 2-rank
+        # and nccl async handles (tests/test_distributed_gpu.py,
+        # tests/test_rccl_rehearsal.py). SMXGB_COMM_OVERLAP=0 disables,
+        # =1 forces even at world 1 (rehearsal).
+        _ov_env = _os.environ.get("SMXGB_COMM_OVERLAP")
+        overlap_ok = hasattr(comm, "allreduce_async_") and (
+            _ov_env == "1" or (_ov_env != "0" and getattr(comm, "world_size", 1) > 1)
+        )
 
-        for d in range(self.D):
+        def hook(d, src, filtered):
             k = 1 << d
-            base = k - 1
-            nodes_d = self.nodes[base : base + k]
-            gh_d = self.node_gh[base : base + k]
-            splits_d = self.splits[base : base + k]
-            counts_d = self.counts[base : base + k]
-            filtered = filter_last and d == self.D - 1
+            acc_d = self.acc[:k]
             par_splits = self.splits[(k >> 1) - 1 : k - 1] if filtered else no_splits
+            src_bins, src_gh = (
+                (st._bins_init, st._gh_init) if src < 0 else (st._bins[src], st._gh[src])
+            )
 
-            if d == 0:
-                _K.grow_make_root(nodes_d, self.hp[0], self.pp[0], self.work[0],
-                                  st.cap, self.rows_per_block, _MAX_BLOCKS_PER_JOB)
-            else:
-                pk = k >> 1
-                pbase = pk - 1
-                _K.grow_make_level(
-                    self.nodes[pbase : pbase + pk], self.splits[pbase : pbase + pk],
-                    self.counts[pbase : pbase + pk], self.node_gh[pbase : pbase + pk],
-                    nodes_d, gh_d, self.hp[d], self.pp[d], self.work[d],
-                    pk, self.rows_per_block, _MAX_BLOCKS_PER_JOB,
-                    1 if filtered else 0,
+            def build(slot_lo, slot_hi):
+                _K.grow_hist_level(
+                    src_bins, src_gh, self.nodes[k - 1 : 2 * k - 1], self.hp[d], self.work[d],
+                    acc_d, k, f, stride, self.n_groups, self.feats_per_group, scale,
+                    self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
+                    slot_lo, slot_hi, par_splits, missing_bin, predicate_only,
                 )
 
-            # a filtered level reads what the level above it read
-            sd = d - 1 if filtered else d
-            src_bins, src_gh, src_rows = (
-                (st._bins_init, st._gh_init, st._rows_init) if sd == 0
-                else (st._bins[sd % 2], st._gh[sd % 2], st._rows[sd % 2])
-            )
-            acc_d = self.acc[:k]
-            acc_d.zero_()
-            # Default ON for real multi-rank groups (the driver's scaling
-            # run): correctness is proven bit-identical under gloo 2-rank
-            # and nccl async handles (tests/test_distributed_gpu.py,
-            # tests/test_rccl_rehearsal.py). SMXGB_COMM_OVERLAP=0 disables,
-            # =1 forces even at world 1 (rehearsal).
-            _ov_env = _os.environ.get("SMXGB_COMM_OVERLAP")
-            overlap = (
-                comm is not None
-                and k >= 4
-                and hasattr(comm, "allreduce_async_")
-                and (_ov_env == "1" or (_ov_env != "0" and getattr(comm, "world_size", 1) > 1))
-            )
-            if overlap:
+            if overlap_ok and k >= 4:
                 # Chunked hist/allreduce pipelining: the collective for the
                 # first half of the level's slots runs on the comm stream
                 # WHILE the compute stream builds the second half's
                 # histograms (the nccl stream only waits on the tensors it
                 # reduces). Fold-compaction per half as below.
                 mid = k >> 1  # even: pairs stay within a half
-                _K.grow_hist_level(
-                    src_bins, src_gh, nodes_d, self.hp[d], self.work[d], acc_d,
-                    k, f, stride, self.n_groups, self.feats_per_group, scale,
-                    self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
-                    0, mid, par_splits, missing_bin, predicate_only,
-                )
+                build(0, mid)
                 c1 = acc_d[0:mid:2] + acc_d[1:mid:2]
                 w1 = comm.allreduce_async_(c1)
-                _K.grow_hist_level(
-                    src_bins, src_gh, nodes_d, self.hp[d], self.work[d], acc_d,
-                    k, f, stride, self.n_groups, self.feats_per_group, scale,
-                    self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
-                    mid, k, par_splits, missing_bin, predicate_only,
-                )
+                build(mid, k)
                 c2 = acc_d[mid::2] + acc_d[mid + 1 :: 2]
                 w2 = comm.allreduce_async_(c2)
                 w1.wait()
@@ -1782,63 +1759,23 @@ class DeviceGrower:
                 w2.wait()
                 acc_d[mid::2] = c2
                 acc_d[mid + 1 :: 2] = c2
+                return
+            build(0, 1 << 30)
+            if k == 1:
+                comm.allreduce_(acc_d)
             else:
-                _K.grow_hist_level(
-                    src_bins, src_gh, nodes_d, self.hp[d], self.work[d], acc_d,
-                    k, f, stride, self.n_groups, self.feats_per_group, scale,
-                    self.rows_per_block, _GROW_HIST_GRID, self.lds_words, self.hist_block,
-                    0, 1 << 30, par_splits, missing_bin, predicate_only,
-                )
-                if comm is not None:
-                    if k == 1:
-                        comm.allreduce_(acc_d)
-                    else:
-                        # Compacted allreduce: of each sibling pair exactly
-                        # one slot was built from rows (the other is all
-                        # zeros — make_level's subtraction trick), so
-                        # folding pairs halves the message without a gather
-                        # kernel. The sum lands back in BOTH child slots;
-                        # convert_level only reads the built one. int64
-                        # adds wrap mod 2^64, matching the kernel's
-                        # unsigned fixed-point.
-                        compact = acc_d[0::2] + acc_d[1::2]
-                        comm.allreduce_(compact)
-                        acc_d[0::2] = compact
-                        acc_d[1::2] = compact
-            hist_d = self.hist_f32[base : base + k]
-            _K.grow_convert_level(acc_d, hist_d, nodes_d, k, self.slots2, scale)
-            if d > 0:
-                pbase = (k >> 1) - 1
-                _K.grow_derive_level(hist_d, self.hist_f32[pbase : pbase + (k >> 1)],
-                                     nodes_d, k, self.slots2)
+                # Compacted allreduce: of each sibling pair exactly one slot
+                # was built from rows (the other is all zeros — make_level's
+                # subtraction trick), so folding pairs halves the message
+                # without a gather kernel. The sum lands back in BOTH child
+                # slots; convert_level only reads the built one. int64 adds
+                # wrap mod 2^64, matching the kernel's unsigned fixed-point.
+                compact = acc_d[0::2] + acc_d[1::2]
+                comm.allreduce_(compact)
+                acc_d[0::2] = compact
+                acc_d[1::2] = compact
 
-            _K.find_splits(
-                hist_d, gh_d, qm._nbins_i32, self.mask, self.mono,
-                self.cands[:k], splits_d, k, f, stride,
-                1 if qm.has_missing else 0, 0, reg_lambda, reg_alpha, gamma, mcw,
-            )
-
-            if self.traverse and d == self.D - 1:
-                # margins updated by traversal: nothing reads the deepest
-                # level's row ids or counts
-                continue
-            if filter_last and d == self.D - 2:
-                continue
-            dst = 1 - d % 2
-            _K.grow_partition_level(
-                src_bins, src_gh, src_rows, st._bins[dst], st._gh[dst], st._rows[dst],
-                nodes_d, self.pp[d], self.work[d], splits_d, counts_d,
-                k, f, missing_bin, _GROW_PART_GRID,
-                1 if d < self.D - 1 else 0,  # last level feeds leaf_update only
-                copy_rows,
-            )
-        # (the grower decides _level0 from whether the root split)
-
-        # the tree's single host drain
-        splits_np = self.splits.cpu().numpy()
-        counts_np = self.counts.cpu().numpy()
-        root_np = self.node_gh[0].cpu().numpy()
-        return splits_np, counts_np, root_np
+        return hook
 
 
 def make_tree_state(qm, gh, sample_rows=None, slot=0):

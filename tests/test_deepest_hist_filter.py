@@ -256,8 +256,8 @@ def test_kernels_against_torch_histogram(dtype, f, stride, rows_per_block):
 
 
 class _OneRank:
-    """Identity communicator: sends DeviceGrower.grow through the per-level
-    Python loop (the distributed path) inside the test process."""
+    """Identity communicator: sends DeviceGrower.grow through the histogram
+    hook of the level loop (the distributed path) inside the test process."""
 
     rank = 0
     world_size = 1
@@ -275,53 +275,110 @@ class _OneRank:
         pass
 
 
-def test_comm_loop_launch_counts_and_results(monkeypatch):
-    """The per-level loop partitions a depth-6 tree D-2 = 4 times with the
-    filter, 5 times with traversal alone and 6 times with the scatter, and
-    grows in every mode the tree the whole-tree enqueue grows."""
+class _HookError(Exception):
+    pass
+
+
+# name: (max_depth, rows, features, max_bin, NaN fraction, bin type). Depths 1
+# and 2 bound the filter (it needs two levels) and the root-only tree. 256
+# bins and the missing slot already make int16 bins (the classic partition
+# and the int16 histogram kernels through the hook); "int16" is that at the
+# scalar feature loop with more bins, "uint8" the staged partition and the
+# u8 kernels. "hook_raises" lets the hook fail once before the same grower
+# grows the tree.
+# The device grower's split scan holds at most 256 real bins per feature
+# (hip.find_splits leaves the kernel above that, the grower does not), so
+# every feature of "int16" goes without a candidate and its tree is the
+# root alone: what that case compares is how both ways run the root level.
+COMM_CASES = {
+    "depth6": (6, 2 * 2048 + 3, 28, 256, 0.2, torch.int16),
+    "depth1": (1, 2 * 2048 + 3, 28, 256, 0.2, torch.int16),
+    "depth2": (2, 2 * 2048 + 3, 28, 256, 0.2, torch.int16),
+    "int16": (6, 4099, 5, 512, 0.2, torch.int16),
+    "uint8": (6, 4099, 28, 256, 0.0, torch.uint8),
+    "hook_raises": (6, 2 * 2048 + 3, 28, 256, 0.2, torch.int16),
+}
+SENTINEL = -7
+
+
+@pytest.mark.parametrize("case", list(COMM_CASES))
+def test_comm_loop_launch_counts_and_results(monkeypatch, case):
+    """With and without a communicator the level loop partitions a depth-D
+    tree's D-2 shallowest levels with the filter, D-1 with traversal alone
+    and all D with the scatter (read from the count heap the partitions
+    write), copies row ids only for the scatter, and grows in every mode the
+    tree the whole-tree enqueue grows without a communicator."""
     from sagemaker_xgboost_container_amd.models.grower import HistGrower
     from sagemaker_xgboost_container_amd.ops import hip
     from sagemaker_xgboost_container_amd.ops.quantize import quantize
 
-    D = 6
-    n = 2 * 2048 + 3
-    X, y = _data(n, 28, seed=14, nan_frac=0.2)
-    qm = quantize(torch.tensor(X, device="cuda"), max_bin=256)
+    D, n, f, max_bin, nan_frac, bin_dtype = COMM_CASES[case]
+    X, y = _data(n, f, seed=14, nan_frac=nan_frac)
+    qm = quantize(torch.tensor(X, device="cuda"), max_bin=max_bin)
+    assert qm.bins.dtype == bin_dtype
     yt = torch.tensor(y, device="cuda")
     gh = torch.stack([0.5 - yt, torch.full_like(yt, 0.25)], dim=1).contiguous()
 
-    calls = []
-    real = hip._K.grow_partition_level
-
-    def counted(*args):
-        calls.append(args[-1])  # copy_rows
-        return real(*args)
-
-    monkeypatch.setattr(hip._K, "grow_partition_level", counted)
-
-    def grow(comm):
-        grower = HistGrower(qm, {"max_depth": D, "eta": 0.3}, comm=comm)
+    def grow(grower):
         tree, leaf_jobs = grower.grow(gh)
         assert grower.grow_path == "device"
         margin = torch.zeros(n, dtype=torch.float32, device="cuda")
         grower.state.update_margins(margin, leaf_jobs)
         return tree, margin.cpu()
 
-    expected_calls = {"scatter": [1] * D, "traverse": [0] * (D - 1), "filter": [0] * (D - 2)}
+    def partitioned_levels(grower):
+        counts = grower._device_grower_for(0).counts.cpu()
+        return [d for d in range(D) if bool(counts[(1 << d) - 1 : (1 << (d + 1)) - 1].any())]
+
+    real_hook = hip.DeviceGrower._comm_hist_hook
+
+    def failing_hook(self, scale, comm):
+        hook = real_hook(self, scale, comm)
+
+        def fail_at_level_2(d, src, filtered):
+            if d == 2:
+                raise _HookError("level 2")
+            hook(d, src, filtered)
+
+        return fail_at_level_2
+
     ref = None
     for deepest, leaf_update in MODES:
         _set_mode(monkeypatch, deepest, leaf_update)
-        tree, margin = grow(None)
-        assert not calls, "the whole-tree enqueue launches its partitions itself"
-        tree_c, margin_c = grow(_OneRank())
-        key = "scatter" if leaf_update == "scatter" else (
-            "traverse" if deepest == "partition" else "filter"
-        )
-        assert calls == expected_calls[key], (key, calls)
-        del calls[:]
-        if ref is None:
-            ref = (tree, margin)
-            assert int(_depths(tree).max()) == D
-        for what, (t, m) in (("enqueue", (tree, margin)), ("comm loop", (tree_c, margin_c))):
-            _assert_same_trees([ref[0]], [t], f"{deepest}/{leaf_update} {what}")
-            assert torch.equal(m, ref[1]), f"{deepest}/{leaf_update} {what}: margins differ"
+        if leaf_update == "scatter":
+            expected = D
+        elif deepest == "partition" or D < 2:
+            expected = D - 1
+        else:
+            expected = D - 2
+        for comm in (None, _OneRank()):
+            what = f"{deepest}/{leaf_update} comm={comm is not None}"
+            grower = HistGrower(qm, {"max_depth": D, "eta": 0.3}, comm=comm)
+            if case == "hook_raises" and comm is not None:
+                with monkeypatch.context() as patch:
+                    patch.setattr(hip.DeviceGrower, "_comm_hist_hook", failing_hook)
+                    with pytest.raises(_HookError, match="level 2"):
+                        grower.grow(gh)
+                device_grower = grower._device_grower_for(0)
+            tree, margin = grow(grower)
+            if case == "hook_raises" and comm is not None:
+                assert grower._device_grower_for(0) is device_grower
+            if ref is None:
+                ref = (tree, margin)
+                depth = int(_depths(tree).max())
+                assert depth == D or case == "int16"
+            # a level whose nodes all stay leaves leaves no count behind
+            assert partitioned_levels(grower) == list(range(min(expected, depth))), what
+
+            # the compact buffers exist now: a second tree leaves their row
+            # ids alone unless the leaf scatter is going to read them
+            row_ids = qm._compact_cache[0][4:6]
+            for buf in row_ids:
+                assert buf.dtype == torch.int32
+                buf.fill_(SENTINEL)
+            tree2, margin2 = grow(grower)
+            untouched = all(bool((buf == SENTINEL).all()) for buf in row_ids)
+            assert untouched == (leaf_update != "scatter" or depth == 0), what
+            for t, m in ((tree, margin), (tree2, margin2)):
+                _assert_same_trees([ref[0]], [t], what)
+                assert torch.equal(m, ref[1]), f"{what}: margins differ"

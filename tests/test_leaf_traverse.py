@@ -312,8 +312,9 @@ def _find_open_port():
 
 
 def _comm_worker(port, q):
-    """Both modes through the communicator's per-level device loop under a
-    1-rank nccl group (the pattern of tests/test_rccl_rehearsal.py)."""
+    """Both modes through the device level loop with the communicator's
+    histogram hook under a 1-rank nccl group (the pattern of
+    tests/test_rccl_rehearsal.py)."""
     try:
         import datetime
 

@@ -355,8 +355,8 @@ def test_training_subsample(hip):
 
 
 class _OneRank:
-    """Identity communicator: sends DeviceGrower.grow through the per-level
-    Python loop (the distributed path) inside the test process."""
+    """Identity communicator: sends DeviceGrower.grow through the histogram
+    hook of the level loop (the distributed path) inside the test process."""
 
     rank = 0
     world_size = 1
@@ -376,8 +376,8 @@ class _OneRank:
 
 @pytest.mark.parametrize("leaf_update", ["traverse", "scatter"])
 def test_per_level_path_selects_the_same_kernel(hip, monkeypatch, leaf_update):
-    """The loop taken with a communicator grows, in both modes, the tree the
-    whole-tree enqueue grows."""
+    """With a communicator the level loop grows, in both modes, the tree it
+    grows without one, and its partitions write the same count heap."""
     from sagemaker_xgboost_container_amd.models.grower import HistGrower
     from sagemaker_xgboost_container_amd.ops.quantize import quantize
 
@@ -389,31 +389,23 @@ def test_per_level_path_selects_the_same_kernel(hip, monkeypatch, leaf_update):
     yt = torch.tensor(y, device="cuda")
     gh = torch.stack([0.5 - yt, torch.full_like(yt, 0.25)], dim=1).contiguous()
 
-    levels = []
-    real = hip._K.grow_partition_level
-
-    def counted(*args):
-        levels.append(args[-1])
-        return real(*args)
-
     def grow(comm):
         grower = HistGrower(qm, {"max_depth": D, "eta": 0.3}, comm=comm)
         tree, leaf_jobs = grower.grow(gh)
         assert grower.grow_path == "device"
         margin = torch.zeros(n, dtype=torch.float32, device="cuda")
         grower.state.update_margins(margin, leaf_jobs)
-        return tree, margin.cpu()
+        return tree, margin.cpu(), grower._device_grower_for(0).counts.cpu()
 
-    monkeypatch.setattr(hip._K, "grow_partition_level", counted)
     ref = None
     for mode in ("classic", "staged"):
         hip.set_partition_mode(mode)
         for comm in (None, _OneRank()):
-            del levels[:]
-            tree, margin = grow(comm)
-            assert bool(levels) == (comm is not None)
+            tree, margin, counts = grow(comm)
             if ref is None:
-                ref = (tree, margin)
+                ref = (tree, margin, counts)
+                assert bool(counts.any())
                 continue
             _assert_same_trees([ref[0]], [tree], f"{mode} comm={comm is not None}")
             assert torch.equal(margin, ref[1]), f"{mode} comm={comm is not None}: margins differ"
+            assert torch.equal(counts, ref[2]), f"{mode} comm={comm is not None}: counts differ"
