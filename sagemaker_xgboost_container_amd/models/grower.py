@@ -530,6 +530,9 @@ class HistGrower:
                 qm._arange_cache = torch.arange(n, dtype=torch.int32, device=self.device)
             if not hasattr(qm, "_nbins_i32"):
                 qm._nbins_i32 = qm.nbins.to(torch.int32).contiguous()
+            warm_tables = getattr(self.backend, "split_tables", None)
+            if warm_tables is not None:
+                warm_tables(qm)  # the split search's wide-feature table
             qm._async_warm = True
         stream = self._class_stream(slot)
         stream.wait_stream(torch.cuda.current_stream(self.device))

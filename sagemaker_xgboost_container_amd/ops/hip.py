@@ -348,6 +348,45 @@ def lambdarank_gradients(plan, margin, y, weight, kind, flags):
     return gh
 
 
+# Supported max_bin range of this backend, stated once. The split search
+# takes any number of bins (features above SPLIT_SCAN_BINS real bins go
+# through the wide split scan). The histogram kernels keep one feature's
+# `stride` slots (real bins + the missing slot) in a single LDS slab at 18
+# bytes a slot, so one feature has to fit the slab: stride <= MAX_HIST_STRIDE,
+# which is max_bin <= 3184 on a matrix with missing values at the default 56
+# KiB slab. Above it a launch would ask for more LDS than a block can have,
+# fail, and leave empty histograms, so check_hist_stride() refuses the matrix.
+SPLIT_SCAN_BINS = 256
+MAX_HIST_STRIDE = min(_LDS_BYTES, 64 * 1024) // 18
+
+
+def check_hist_stride(qm):
+    """Refuse a matrix whose features do not fit the histogram kernels' LDS
+    slab (see MAX_HIST_STRIDE) instead of growing root-only trees."""
+    if qm.stride > MAX_HIST_STRIDE:
+        raise ValueError(
+            f"max_bin too large for the HIP histogram kernels: the matrix has {qm.stride} "
+            f"histogram slots per feature, at most {MAX_HIST_STRIDE} are supported "
+            f"(max_bin <= {MAX_HIST_STRIDE - 1} with missing values)"
+        )
+
+
+def split_tables(qm, device=None):
+    """The split search's per-matrix device tables, built once from the
+    matrix's `nbins` and cached on it: nbins as int32 [f] and the int32
+    indices of the wide features (more than SPLIT_SCAN_BINS real bins; empty
+    when there is none)."""
+    wide = getattr(qm, "_wide_feats_i32", None)
+    if wide is None:
+        device = device if device is not None else qm.bins.device
+        nbins = qm.nbins.cpu()
+        if not hasattr(qm, "_nbins_i32"):
+            qm._nbins_i32 = nbins.to(torch.int32).to(device).contiguous()
+        wide = (nbins > SPLIT_SCAN_BINS).nonzero().flatten().to(torch.int32).to(device)
+        qm._wide_feats_i32 = wide.contiguous()
+    return qm._nbins_i32, qm._wide_feats_i32
+
+
 def _padded_words(pairs):
     """LDS u64 words for `pairs` histogram slots incl. bank-skew padding."""
     return (pairs + (pairs >> 3) + 1) * 2
@@ -412,6 +451,7 @@ def _pack_jobs_and_map(fields_list, blocks_per_job):
 
 
 def build_histograms(qm, gh, rowbuf, jobs, scale):
+    check_hist_stride(qm)
     f = qm.num_col
     stride = qm.stride
     groups = _feature_groups(f, stride)
@@ -467,25 +507,19 @@ def find_splits(
 ):
     """Fused HIP split scan: 2 kernel launches per level, zero host syncs.
 
+    A matrix with features of more than 256 real bins (max_bin > 256) adds
+    one launch between the two: the wide split scan over those features,
+    named by the table split_tables() caches on `qm`.
+
     A matrix with categorical columns (qm.is_cat) adds two launches: the
     category-set scan of those features between the numeric scan and the
     reduce, and the gather of the winners' sets into "cat_bits" [k, 8]
     int32 (torch_ref.find_splits states the rule). Without such a column
-    nothing else is launched and only "packed" is returned.
-
-    Falls back to the torch reference when a feature has > 256 real bins
-    (max_bin > 256 configurations)."""
+    nothing else is launched and only "packed" is returned."""
     k = hist.shape[0]
     f = qm.num_col
     stride = qm.stride
-    if not hasattr(qm, "_nbins_i32"):
-        qm._nbins_i32 = qm.nbins.to(torch.int32).contiguous()
-    if int(qm._nbins_i32.max()) > 256:
-        return torch_ref.find_splits(
-            hist, parent_sum, qm, reg_lambda=reg_lambda, reg_alpha=reg_alpha, gamma=gamma,
-            min_child_weight=min_child_weight, feature_mask=feature_mask, monotone=monotone,
-            max_cat_to_onehot=max_cat_to_onehot, max_cat_threshold=max_cat_threshold,
-        )
+    nbins_i32, wide_feats = split_tables(qm, hist.device)
     if getattr(qm, "is_cat", None) is not None:
         return _find_splits_cat(
             hist, parent_sum, qm, reg_lambda, reg_alpha, gamma, min_child_weight,
@@ -506,8 +540,8 @@ def find_splits(
     cands = torch.empty((k, f, 5), dtype=torch.float32, device=device)
     out = torch.empty((k, 6), dtype=torch.float32, device=device)
     _K.find_splits(
-        hist.contiguous(), parent_sum.contiguous(), qm._nbins_i32, mask, mono, cands, out,
-        k, f, stride, 1 if qm.has_missing else 0, per_node,
+        hist.contiguous(), parent_sum.contiguous(), nbins_i32, wide_feats, mask, mono, cands,
+        out, k, f, stride, 1 if qm.has_missing else 0, per_node,
         reg_lambda, reg_alpha, gamma, min_child_weight,
     )
     return {"packed": out}
@@ -552,7 +586,7 @@ def _find_splits_cat(hist, parent_sum, qm, reg_lambda, reg_alpha, gamma, min_chi
     cand_bits = torch.empty((k, f, 8), dtype=torch.int32, device=device)
     cat_bits = torch.empty((k, 8), dtype=torch.int32, device=device)
     _K.find_splits_cat(
-        hist.contiguous(), parent_sum.contiguous(), qm._nbins_i32, num_mask, per_node,
+        hist.contiguous(), parent_sum.contiguous(), *split_tables(qm, device), num_mask, per_node,
         cat_mask, per_node, mono, cands, out, is_cat_u8, cat_feats, cand_bits, cat_bits,
         k, f, qm.stride, 1 if qm.has_missing else 0,
         reg_lambda, reg_alpha, gamma, min_child_weight,
@@ -1509,8 +1543,7 @@ class DeviceGrower:
             self.allowed = torch.empty((H, W), dtype=torch.int32, device=device)
             self.allowed[0].fill_(-1)
             self.node_mask = torch.empty((max_k, f), dtype=torch.uint8, device=device)
-        if not hasattr(qm, "_nbins_i32"):
-            qm._nbins_i32 = qm.nbins.to(torch.int32).contiguous()
+        split_tables(qm)
 
     def _enqueue_body(self, gh_init, scale, split_params, rootsum=None, alloc_free=False,
                       hist_hook=None):
@@ -1550,7 +1583,7 @@ class DeviceGrower:
             st._bins[1], st._gh[1], st._rows[1],
             self.nodes, self.node_gh, self.splits, self.counts,
             self.hist_f32, self.acc, self.cands, self.hp, self.pp, self.work,
-            qm._nbins_i32, self.mask, self.mono,
+            *split_tables(qm), self.mask, self.mono,
             self.inter_union, self.allowed, self.node_mask, scale,
             self.D, st.cap, f, stride, self.n_groups, self.feats_per_group,
             self.lds_words, 1 if qm.has_missing else 0, missing_bin,
@@ -1779,6 +1812,7 @@ class DeviceGrower:
 
 
 def make_tree_state(qm, gh, sample_rows=None, slot=0):
+    check_hist_stride(qm)
     if _os.environ.get("SMXGB_PIPELINE") == "v1":
         return _V1TreeState(qm, gh, sample_rows)
     return TreeState(qm, gh, sample_rows, slot=slot)
