@@ -1,12 +1,19 @@
-"""Ranking gradient on an MSLR-like set: the sampled pair method (one random
-partner per document, a Python loop over the query groups) against the
-top-k LambdaRank kernels of csrc/smxgb_rank.hip, in one process.
+"""Ranking on an MSLR-like set, two arms, each comparing two paths in one
+process.
 
-    python benchmarks/bench_ranking.py [--rows 2400000] [--reps 3] [--rounds 3]
+gradient: the sampled pair method (one random partner per document, a Python
+loop over the query groups) against the top-k LambdaRank kernels of
+csrc/smxgb_rank.hip.
+eval: ndcg@10, ndcg and map through the per-group Python loop of
+models/eval_metrics.py (what SMXGB_FORCE_TORCH_OPS=1 runs) against the
+kernels of csrc/smxgb_rank_metric.hip, and a top-k training run that watches
+its training set with either.
 
-Prints one JSON line: gradient milliseconds per call of each path (median
-and spread over the alternating repetitions) and depth-6 training rounds
-per second with each path. Needs an MI355X.
+    python benchmarks/bench_ranking.py [--arm all] [--rows 2400000] [--reps 3] [--rounds 3]
+
+Prints one JSON line: milliseconds per call of each path (median and spread
+over the alternating repetitions) and depth-6 training rounds per second
+with each path. Needs an MI355X.
 """
 import argparse
 import json
@@ -21,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from sagemaker_xgboost_container_amd.data.dmatrix import DMatrix  # noqa: E402
-from sagemaker_xgboost_container_amd.models import trainer  # noqa: E402
+from sagemaker_xgboost_container_amd.models import eval_metrics, trainer  # noqa: E402
 from sagemaker_xgboost_container_amd.models.objectives import create_objective  # noqa: E402
 
 
@@ -54,13 +61,13 @@ def time_gradients(objective, margin, y, reps):
     return out
 
 
-def time_training(params, dtrain, rounds):
+def time_training(params, dtrain, rounds, evals=None):
     """Seconds per round: (rounds + 1)-round run minus a 1-round run, so that
     the set-up (upload, quantisation) cancels."""
     def run(r):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        trainer.train(params, dtrain, num_boost_round=r, verbose_eval=False)
+        trainer.train(params, dtrain, num_boost_round=r, evals=evals, verbose_eval=False)
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
@@ -68,8 +75,58 @@ def time_training(params, dtrain, rounds):
     return (run(rounds + 1) - one) / rounds
 
 
+def loop_evaluate(metric_name, margin, y, weight, objective, group_ptr=None, rank_plans=None):
+    """evaluate() as it runs without the kernels: the per-group loop."""
+    base, _, k = metric_name.partition("@")
+    fn = {"ndcg": eval_metrics.ndcg, "map": eval_metrics.mean_ap}[base]
+    return fn(margin, y, objective, k=int(k) if k else None, group_ptr=group_ptr)
+
+
+def eval_arm(args, dtrain, sizes, margin, yd):
+    """Host milliseconds per evaluate() call, which ends in the readback of
+    the value, and rounds per second of a run that watches its training set."""
+    objective = create_objective("rank:ndcg", {})
+    ptr = np.concatenate([[0], np.cumsum(sizes)])
+    plans = {}
+    paths = {
+        "loop": lambda name: loop_evaluate(name, margin, yd, None, objective, group_ptr=ptr),
+        "kernels": lambda name: eval_metrics.evaluate(
+            name, margin, yd, None, objective, group_ptr=ptr, rank_plans=plans),
+    }
+    metrics = ["ndcg@10", "ndcg", "map"]
+    values = {p: {} for p in paths}
+    ms = {p: {name: [] for name in metrics} for p in paths}
+    for rep in range(args.reps + 1):  # the first pass warms up (plans, IDCG, allocator)
+        for name in metrics:
+            for p, fn in paths.items():  # alternate: both paths see the same machine state
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                values[p][name] = fn(name)
+                torch.cuda.synchronize()
+                if rep:
+                    ms[p][name].append((time.perf_counter() - t0) * 1e3)
+    params = {"objective": "rank:ndcg", "lambdarank_pair_method": "topk", "eval_metric": "ndcg",
+              "max_depth": 6, "eta": 0.3, "device": "cuda"}
+    out = {}
+    for p in paths:
+        device_evaluate = trainer.evaluate_metric
+        if p == "loop":
+            trainer.evaluate_metric = loop_evaluate
+        try:
+            sec = time_training(params, dtrain, args.rounds, evals=[(dtrain, "train")])
+        finally:
+            trainer.evaluate_metric = device_evaluate
+        out[p] = {"round_s": sec, "rounds_per_s": 1.0 / sec}
+        for name in metrics:
+            t = ms[p][name]
+            out[p][name] = {"value": values[p][name], "ms_median": statistics.median(t),
+                            "ms_min": min(t), "ms_max": max(t)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arm", choices=["gradient", "eval", "all"], default="all")
     ap.add_argument("--rows", type=int, default=2_400_000)
     ap.add_argument("--features", type=int, default=136)
     ap.add_argument("--reps", type=int, default=3)
@@ -83,10 +140,13 @@ def main():
     yd = torch.from_numpy(y).to(dev)
     # margins of a partly trained model: labels plus noise, so ranks are mixed
     margin = (yd * 0.5 + torch.randn(args.rows, device=dev, generator=torch.Generator(dev).manual_seed(1)))
+    result = {"rows": args.rows, "groups": len(sizes), "mean_group": args.rows / len(sizes)}
+    if args.arm != "gradient":
+        result["eval"] = eval_arm(args, dtrain, sizes, margin, yd)
     paths = {
         "sampled": {"objective": "rank:ndcg"},
         "topk": {"objective": "rank:ndcg", "lambdarank_pair_method": "topk"},
-    }
+    } if args.arm != "eval" else {}
     objectives = {}
     for name, p in paths.items():
         objectives[name] = create_objective(p["objective"], p)
@@ -96,7 +156,6 @@ def main():
     for _ in range(args.reps):  # alternate: both paths see the same machine state
         for name in paths:
             grad_ms[name] += time_gradients(objectives[name], margin, yd, 1)
-    result = {"rows": args.rows, "groups": len(sizes), "mean_group": args.rows / len(sizes)}
     for name, p in paths.items():
         ms = grad_ms[name]
         sec = time_training(dict(p, max_depth=6, eta=0.3, device="cuda"), dtrain, args.rounds)

@@ -5,6 +5,7 @@ training: predictions never leave HBM). AUC uses a sort-based exact
 computation. Names/directions match constants/xgb_constants.py.
 """
 import math
+import os
 
 import torch
 
@@ -162,7 +163,15 @@ def mphe(pred, y, weight=None, slope=1.0):
     return float((w * loss).sum() / w.sum())
 
 
-def _group_bounds(objective, n, device):
+def _group_bounds(objective, n, device, group_ptr=None):
+    """Query groups as (start, end) pairs: `group_ptr`, the (G+1,) boundaries
+    of the scored data set itself, where given; else the training groups the
+    objective holds, where they cover n rows; else one query."""
+    if group_ptr is not None:
+        p = [int(v) for v in group_ptr]
+        if not p or p[0] != 0 or p[-1] != n:
+            raise ValueError("group_ptr must rise from 0 to the row count")
+        return list(zip(p[:-1], p[1:]))
     ptr = getattr(objective, "group_ptr", None)
     if ptr is not None and int(ptr[-1]) == n:
         p = ptr.tolist()
@@ -170,10 +179,10 @@ def _group_bounds(objective, n, device):
     return [(0, n)]
 
 
-def ndcg(score, y, objective=None, k=None):
+def ndcg(score, y, objective=None, k=None, group_ptr=None):
     """Mean NDCG(@k) over query groups (exponential gain)."""
     total = 0.0
-    bounds = _group_bounds(objective, score.shape[0], score.device) if objective else [(0, score.shape[0])]
+    bounds = _group_bounds(objective, score.shape[0], score.device, group_ptr)
     for a, b in bounds:
         s, rel = score[a:b], y[a:b]
         m = b - a
@@ -187,10 +196,10 @@ def ndcg(score, y, objective=None, k=None):
     return total / len(bounds)
 
 
-def mean_ap(score, y, objective=None, k=None):
+def mean_ap(score, y, objective=None, k=None, group_ptr=None):
     """Mean average precision over query groups (binary relevance)."""
     total = 0.0
-    bounds = _group_bounds(objective, score.shape[0], score.device) if objective else [(0, score.shape[0])]
+    bounds = _group_bounds(objective, score.shape[0], score.device, group_ptr)
     for a, b in bounds:
         s, rel = score[a:b], (y[a:b] > 0).float()
         m = b - a
@@ -236,10 +245,12 @@ _SQRT_METRICS = {"rmse", "rmsle"}
 _GROUP_METRICS = {"ndcg", "map"}
 
 
-def metric_mass(metric_name, y, weight, objective):
+def metric_mass(metric_name, y, weight, objective, group_ptr=None):
     """The aggregation weight for one rank's metric value (see above)."""
     base = metric_name.partition("@")[0]
     if base in _GROUP_METRICS:
+        if group_ptr is not None:
+            return float(len(group_ptr) - 1)
         return float(len(_group_bounds(objective, y.shape[0], y.device))) if objective else 1.0
     if base == "cox-nloglik":
         return max(float((y > 0).sum()), 1.0)
@@ -258,8 +269,31 @@ def from_agg_space(metric_name, value):
     return math.sqrt(max(value, 0.0)) if metric_name.partition("@")[0] in _SQRT_METRICS else value
 
 
-def evaluate(metric_name, margin, y, weight, objective):
-    """Compute one named metric from raw margins via the objective transform."""
+def _device_rank_metric(name, margin, y, objective, k, group_ptr, plans):
+    """ndcg / map through the HIP kernels (ops/hip.rank_metric): one scalar
+    read back, no per-group host work. `plans` caches the work tables by k
+    for a caller that scores the same data set every round."""
+    from ..ops import hip
+
+    n = margin.shape[0]
+    plan = plans.get(k) if plans is not None else None
+    if plan is None or plan["n"] != n:
+        if group_ptr is None:
+            ptr = getattr(objective, "group_ptr", None)
+            group_ptr = ptr.tolist() if ptr is not None and int(ptr[-1]) == n else [0, n]
+        plan = hip.rank_metric_plan(group_ptr, k, y, margin.device)
+        if plans is not None:
+            plans[k] = plan
+    return hip.rank_metric(plan, name, margin)[0]
+
+
+def evaluate(metric_name, margin, y, weight, objective, group_ptr=None, rank_plans=None):
+    """Compute one named metric from raw margins via the objective transform.
+
+    group_ptr: the (G+1,) query group boundaries of the scored data set, for
+    ndcg / map; None looks the groups up through the objective. rank_plans: a
+    dict the caller keeps with the data set, in which the device path of
+    ndcg / map caches its work tables."""
     name = metric_name
     threshold = None
     if "@" in name:
@@ -326,10 +360,13 @@ def evaluate(metric_name, margin, y, weight, objective):
         return gamma_deviance(pred, y, weight)
     if name == "tweedie-nloglik":
         return tweedie_nloglik(pred, y, weight, rho=float(objective.params.get("tweedie_variance_power", 1.5)))
-    if name == "ndcg":
-        return ndcg(margin, y, objective, k=int(threshold) if threshold else None)
-    if name == "map":
-        return mean_ap(margin, y, objective, k=int(threshold) if threshold else None)
+    if name in ("ndcg", "map"):
+        k = int(threshold) if threshold else None
+        if (margin.is_cuda and margin.dim() == 1 and margin.numel() and y.numel() == margin.numel()
+                and os.environ.get("SMXGB_FORCE_TORCH_OPS") != "1"):
+            return _device_rank_metric(name, margin, y, objective, k, group_ptr, rank_plans)
+        fn = ndcg if name == "ndcg" else mean_ap
+        return fn(margin, y, objective, k=k, group_ptr=group_ptr)
     if name == "cox-nloglik":
         return cox_nloglik(margin, y)
     if name == "aft-nloglik":

@@ -236,6 +236,14 @@ class _EvalSet:
         self.name = name
         self.csr = None
         self.is_train = dmatrix is train_dmatrix
+        # ndcg / map score this set by its own query groups: (G+1,) row
+        # boundaries, None without group info (or with sizes that do not
+        # add up to the rows, as eval_metrics._group_bounds treats them)
+        group = dmatrix.get_group() if hasattr(dmatrix, "get_group") else None
+        self.group_ptr = None
+        if group is not None and int(np.sum(group)) == dmatrix.num_row():
+            self.group_ptr = np.concatenate([[0], np.cumsum(group)]).astype(np.int64)
+        self.rank_plans = {}  # device work tables of ndcg / map, by k
         if self.is_train:
             self.X = train_X
             self.y = train_y
@@ -645,9 +653,11 @@ def train(
                     results.append((es.name, metric_name, 0.0))
                     masses.append(0.0)
                     continue
-                value = evaluate_metric(metric_name, m, es.y, es.w, objective)
+                value = evaluate_metric(metric_name, m, es.y, es.w, objective,
+                                        group_ptr=es.group_ptr, rank_plans=es.rank_plans)
                 results.append((es.name, metric_name, value))
-                masses.append(eval_metrics.metric_mass(metric_name, es.y, es.w, objective))
+                masses.append(eval_metrics.metric_mass(metric_name, es.y, es.w, objective,
+                                                       group_ptr=es.group_ptr))
             if feval is not None and not empty:
                 m_np = m.cpu().numpy()
                 custom = feval(m_np, es.dmatrix)

@@ -3389,6 +3389,7 @@ void init_shap_compact_kernels(pybind11::module_& m);
 void init_sampling_kernels(pybind11::module_& m);
 void init_quantile_kernels(pybind11::module_& m);
 void init_rank_kernels(pybind11::module_& m);
+void init_rank_metric_kernels(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_text_parsers(m);
@@ -3397,6 +3398,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_sampling_kernels(m);
   init_quantile_kernels(m);
   init_rank_kernels(m);
+  init_rank_metric_kernels(m);
   m.def("hist_build", &hist_build, "batched LDS-staged fixed-point histogram build");
   m.def("hist_convert", &hist_convert, "fixed-point -> float32 histogram convert");
   m.def("partition", &partition, "batched two-ended row partition");

@@ -214,6 +214,39 @@ LAMBDARANK_CAP = int(_K.lambdarank_cap())
 LAMBDARANK_FLAG_NORM, LAMBDARANK_FLAG_SCORE, LAMBDARANK_FLAG_EXP_GAIN = 1, 2, 4
 
 
+def _group_tiles(group_ptr, cap, tile_docs, max_groups):
+    """Packs runs of consecutive query groups into tiles of at most
+    `tile_docs` documents and `max_groups` groups. Returns the boundaries as
+    an int64 array, the tiles as (first group, group count), and the groups
+    of more than `cap` documents, which no tile holds, as (group, first row,
+    size)."""
+    ptr = (group_ptr.detach().cpu().numpy() if isinstance(group_ptr, torch.Tensor)
+           else np.asarray(group_ptr)).astype(np.int64)
+    if ptr.ndim != 1 or ptr.size < 2 or ptr[0] != 0 or (np.diff(ptr) < 0).any():
+        raise ValueError("group_ptr must rise from 0 to the row count")
+    n = int(ptr[-1])
+    if not (1 <= n < 2**31):
+        raise ValueError("row count must be in [1, 2^31)")
+    sizes = np.diff(ptr)
+    if not (sizes[sizes <= cap].max(initial=1) <= tile_docs <= cap):
+        raise ValueError(f"tile_docs must hold the largest tiled group and be at most {cap}")
+    tiles, stream = [], []
+    first, docs = 0, 0
+    for g, m in enumerate(sizes.tolist()):
+        if m > cap or docs + m > tile_docs or g - first >= max_groups:
+            if g > first:
+                tiles.append((first, g - first))
+            first, docs = g, 0
+        if m > cap:
+            stream.append((g, int(ptr[g]), m))
+            first = g + 1
+        else:
+            docs += m
+    if len(sizes) > first:
+        tiles.append((first, len(sizes) - first))
+    return ptr, tiles, stream
+
+
 def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None):
     """Work tables of the top-k LambdaRank gradient (csrc/smxgb_rank.hip)
     for fixed query groups, built once on the host.
@@ -230,31 +263,9 @@ def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None):
         raise ValueError(
             f"lambdarank_num_pair_per_sample must be in [1, {torch_ref.LAMBDARANK_MAX_K}]"
         )
-    ptr = (group_ptr.detach().cpu().numpy() if isinstance(group_ptr, torch.Tensor)
-           else np.asarray(group_ptr)).astype(np.int64)
-    if ptr.ndim != 1 or ptr.size < 2 or ptr[0] != 0 or (np.diff(ptr) < 0).any():
-        raise ValueError("group_ptr must rise from 0 to the row count")
+    ptr, tiles, stream = _group_tiles(group_ptr, cap, tile_docs, int(_K.lambdarank_max_groups()))
     n = int(ptr[-1])
-    if not (1 <= n < 2**31):
-        raise ValueError("row count must be in [1, 2^31)")
-    sizes = np.diff(ptr)
-    if not (sizes[sizes <= cap].max(initial=1) <= tile_docs <= cap):
-        raise ValueError(f"tile_docs must hold the largest tiled group and be at most {cap}")
-    max_groups = int(_K.lambdarank_max_groups())
-    tiles, stream = [], []
-    first, docs = 0, 0
-    for g, m in enumerate(sizes.tolist()):
-        if m > cap or docs + m > tile_docs or g - first >= max_groups:
-            if g > first:
-                tiles.append((first, g - first))
-            first, docs = g, 0
-        if m > cap:
-            stream.append((int(ptr[g]), m))
-            first = g + 1
-        else:
-            docs += m
-    if len(sizes) > first:
-        tiles.append((first, len(sizes) - first))
+    stream = [(gs, m) for _, gs, m in stream]
     dev = torch.device(device)
     kk = min(k, cap)
     disc = 1.0 / np.log2(np.arange(kk, dtype=np.float64) + 2.0)
@@ -346,6 +357,95 @@ def lambdarank_gradients(plan, margin, y, weight, kind, flags):
         rows += step
     gh._smxgb_absmax = pmax.amax(dim=0).contiguous()
     return gh
+
+
+RANK_METRIC_CAP = int(_K.rank_metric_cap())
+
+
+def rank_metric_plan(group_ptr, k, y, device="cuda", tile_docs=None):
+    """Work tables of the ranking metrics ndcg[@k] / map[@k]
+    (csrc/smxgb_rank_metric.hip) for one data set and one k, built once.
+
+    group_ptr: (G+1,) boundaries rising from 0 to n; k: the cut-off, None for
+    none; y: the (n,) labels, which the plan keeps on the device. Groups are
+    packed into tiles as lambdarank_plan packs them; a group of more than
+    RANK_METRIC_CAP documents goes through the stream kernels. The IDCG of
+    every group is added by the first ndcg call. The values do not depend on
+    the packing, which is what `tile_docs` is there to show."""
+    cap = RANK_METRIC_CAP
+    tile_docs = cap if tile_docs is None else int(tile_docs)
+    if k is not None and not (1 <= int(k) < 2**31):
+        raise ValueError("k must be None or in [1, 2^31)")
+    k = 0 if k is None else int(k)  # the kernels' "no cut-off"
+    ptr, tiles, stream = _group_tiles(group_ptr, cap, tile_docs, int(_K.rank_metric_max_groups()))
+    n = int(ptr[-1])
+    dev = torch.device(device)
+    y = torch.as_tensor(y)
+    if y.dim() != 1 or y.numel() != n:
+        raise ValueError("y must be 1-d with the row count of group_ptr")
+    y = y.to(device=dev, dtype=torch.float32).contiguous()
+    chunk = int(_K.rank_metric_stream_chunk())
+    chunks = max([-(-(min(k, m) if k else m) // chunk) for _, _, m in stream], default=0)
+    # relevant documents of each stream group: with a cut-off the kernels
+    # read its first k positions only
+    n_pos = torch.stack([(y[gs:gs + m] > 0).sum() for _, gs, m in stream]).tolist() if stream else []
+    return {
+        "n": n,
+        "k": k,
+        "n_groups": ptr.size - 1,
+        "y": y,
+        "group_ptr": torch.from_numpy(ptr.astype(np.int32)).to(dev),
+        "tiles": torch.tensor(tiles, dtype=torch.int32).reshape(-1, 2).to(dev),
+        "n_tiles": len(tiles),
+        "stream": [(g, gs, m, int(p)) for (g, gs, m), p in zip(stream, n_pos)],
+        "disc": torch.from_numpy(1.0 / np.log2(np.arange(cap, dtype=np.float64) + 2.0)).to(dev),
+        "idcg": None,
+        "chunk_h": torch.empty(chunks, dtype=torch.int32, device=dev),
+        "part": torch.empty(chunks, dtype=torch.float64, device=dev),
+    }
+
+
+def _rank_metric_values(plan, kind, margin, idcg):
+    """One float64 value per group; `idcg` empty: the DCG (kind 0)."""
+    dev = margin.device
+    k, y = plan["k"], plan["y"]
+    value = torch.empty(plan["n_groups"], dtype=torch.float64, device=dev)
+    if plan["n_tiles"]:
+        _K.rank_metric_tile(margin, y, plan["group_ptr"], plan["tiles"], plan["disc"], idcg, k,
+                            kind, value)
+    for g, gs, m, n_pos in plan["stream"]:
+        keys = torch.empty(m, dtype=torch.int64, device=dev)
+        _K.rank_metric_keys(margin[gs:gs + m], keys)
+        _K.rank_metric_stream(torch.sort(keys).values, y, gs, m, k, kind, n_pos, idcg, g,
+                              plan["chunk_h"], plan["part"], value)
+    return value
+
+
+def rank_metric(plan, kind, margin):
+    """ndcg or map (`kind`) of `margin` over the plan's groups, on the
+    device; the rule and the float64 reference are torch_ref.rank_metric.
+    Returns (mean, per_group): the metric as a float, the one readback of
+    the call, and the (G,) float64 device tensor it is the mean of. The
+    result is the same bit for bit from call to call and does not depend on
+    the plan's tile packing."""
+    n = plan["n"]
+    if kind not in torch_ref.RANK_METRIC_KINDS:
+        raise ValueError(f"kind must be 'ndcg' or 'map', got {kind!r}")
+    if not margin.is_cuda or margin.dim() != 1 or margin.numel() != n:
+        raise ValueError("margin must be a 1-d ROCm device tensor with the plan's row count")
+    if margin.device != plan["y"].device:
+        raise ValueError("margin must live on the plan's device")
+    margin = margin.to(torch.float32).contiguous()
+    none = torch.empty(0, dtype=torch.float64, device=margin.device)
+    idcg = none
+    if kind == "ndcg":
+        if plan["idcg"] is None:  # labels and k only: once per plan
+            plan["idcg"] = _rank_metric_values(plan, 0, plan["y"], none)
+        idcg = plan["idcg"]
+    value = _rank_metric_values(plan, torch_ref.RANK_METRIC_KINDS[kind], margin, idcg)
+    mean = torch.empty(1, dtype=torch.float64, device=margin.device)
+    _K.rank_metric_mean(value, mean)
+    return float(mean), value
 
 
 # Supported max_bin range of this backend, stated once. The split search

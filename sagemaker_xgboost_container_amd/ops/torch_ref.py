@@ -1323,3 +1323,61 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
         return {"g": g_out, "h": h_out, "mass": a_out}
     gh = np.stack([g_out, h_out], axis=1).astype(np.float32)
     return torch.from_numpy(gh).to(margin.device)
+
+
+# ---------------------------------------------------------------------------
+# Ranking metrics ndcg[@k] and map[@k], one value per query group
+# ---------------------------------------------------------------------------
+RANK_METRIC_KINDS = {"ndcg": 0, "map": 1}
+
+
+def rank_metric(kind, margin, y, group_ptr=None, k=None):
+    """ndcg or map of every query group, in float64: the rule the HIP
+    kernels of csrc/smxgb_rank_metric.hip follow. Returns a (G,) float64
+    tensor; the metric is its mean.
+
+    Per group [group_ptr[i], group_ptr[i+1]) of m documents (no group_ptr:
+    one group):
+      rank   descending margin; a NaN margin ranks above +inf, -0.0 equal
+             to +0.0, equal margins by ascending row
+      top    m without k, else min(k, m)
+      ndcg   dcg = sum_{p < top} (2^y_p - 1) / log2(p + 2); idcg the same
+             sum over the labels sorted descending; dcg / idcg, 1.0 where
+             idcg <= 0. Labels are any finite float32.
+      map    hit_p = y_p > 0; sum_{p < top} hit_p * hits_through_p / (p + 1)
+             over n_pos, the relevant documents of the whole group; 1.0
+             where n_pos == 0
+    An empty group scores 1.0."""
+    import numpy as np
+
+    if kind not in RANK_METRIC_KINDS:
+        raise ValueError(f"kind must be 'ndcg' or 'map', got {kind!r}")
+    if k is not None and int(k) < 1:
+        raise ValueError("k must be at least 1")
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+    s_all = as_np(margin).astype(np.float32).astype(np.float64).ravel()
+    y_all = as_np(y).astype(np.float32).astype(np.float64).ravel()
+    n = s_all.size
+    ptr = np.array([0, n]) if group_ptr is None else as_np(group_ptr).astype(np.int64)
+    if y_all.size != n or ptr[0] != 0 or ptr[-1] != n or (np.diff(ptr) < 0).any():
+        raise ValueError("y must match margin and group_ptr must rise from 0 to the row count")
+    out = np.ones(ptr.size - 1, dtype=np.float64)
+    for g, (a, b) in enumerate(zip(ptr[:-1].tolist(), ptr[1:].tolist())):
+        m = b - a
+        top = m if k is None else min(int(k), m)
+        s, lab = s_all[a:b], y_all[a:b]
+        nan = np.isnan(s)
+        # stable, so equal keys keep their row order; the last key leads
+        order = np.lexsort((np.where(nan, 0.0, -s), ~nan))[:top]
+        pos = np.arange(top, dtype=np.float64)
+        if kind == "ndcg":
+            disc = 1.0 / np.log2(pos + 2.0)
+            dcg = float(((np.exp2(lab[order]) - 1.0) * disc).sum())
+            idcg = float(((np.exp2(-np.sort(-lab)[:top]) - 1.0) * disc).sum())
+            out[g] = dcg / idcg if idcg > 0 else 1.0
+        else:
+            hit = (lab[order] > 0).astype(np.float64)
+            n_pos = int((lab > 0).sum())
+            if n_pos:
+                out[g] = float((hit * np.cumsum(hit) / (pos + 1.0)).sum()) / n_pos
+    return torch.from_numpy(out)
