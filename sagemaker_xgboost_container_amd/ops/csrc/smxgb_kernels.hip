@@ -837,6 +837,39 @@ __device__ inline void hist_wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// Add the slab's non-zero sums of (slot, feature group fg) to the level's
+// accumulator and leave the slab all zero for whatever the block builds next.
+// The caller puts a barrier between the last LDS atomic and this, and one
+// after it before the next.
+__device__ inline void hist_flush_slab(unsigned long long* lhist,
+                                       unsigned long long* __restrict__ out, int slot, int fg,
+                                       int nfeat, int stride, int feats_per_group) {
+  const int fg_start = fg * feats_per_group;
+  const int nf_group = min(feats_per_group, nfeat - fg_start);
+  const int lds_words = nf_group * stride * 2;
+  const int hofs = (int)lds_half_words(nf_group * stride);
+  unsigned long long* gout = out + ((long long)slot * nfeat + fg_start) * (long long)stride * 2;
+  for (int i = threadIdx.x; i < lds_words; i += blockDim.x) {
+    const int idx = lds_pad_slot(i >> 1) + ((i & 1) ? hofs : 0);
+    const unsigned long long v = lhist[idx];
+    if (v) {
+      atomicAdd(&gout[i], v);
+      lhist[idx] = 0ull;
+    }
+  }
+}
+
+// Work distribution: the level's virtual blocks, numbered feature-group-major
+// (vb = fg * hist_total + hvb), are dealt out in contiguous ranges, block b
+// taking [b * total / grid, (b + 1) * total / grid). Neighbours in that order
+// nearly always share slot and group, so the slab stays live across them: it
+// is zeroed when the block first has work, flushed (hist_flush_slab) only
+// where (slot, fg) changes and once at the end. The sums are integers, so
+// which block adds a row changes no bit. A virtual block still walks its
+// slot's rows as chunk `hvb - hist_prefix[slot]` of `nb`: rows_per_block sets
+// the balance between blocks, the grid the number of flushes (at most
+// grid + k * n_groups per launch). Feature groups only shrink with fg, so
+// the first zeroing covers every later layout of the block.
 template <typename BinT, int BLOCK, int FILTER>
 __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
     const BinT* __restrict__ bins_c, const float2* __restrict__ gh_c,
@@ -849,11 +882,15 @@ __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
   constexpr int HROWS = HIST_ROWS_IN_FLIGHT;
   const float scale_g = 8589934592.0f / fmaxf(gh_max[0], 1e-30f);
   const float scale_h = 8589934592.0f / fmaxf(gh_max[1], 1e-30f);
-  const int total = work->hist_total * n_groups;
+  const int level_blocks = work->hist_total;
+  const long long total = (long long)level_blocks * n_groups;
+  const int vb_end = (int)((blockIdx.x + 1ll) * total / gridDim.x);
+  // the (slot, feature group) whose sums the slab holds; -1: nothing yet
+  int live_slot = -1, live_fg = 0;
 
-  for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
-    const int fg = vb % n_groups;
-    const int hvb = vb / n_groups;
+  for (int vb = (int)(blockIdx.x * total / gridDim.x); vb < vb_end; ++vb) {
+    const int fg = vb / level_blocks;
+    const int hvb = vb - fg * level_blocks;
     const int slot = find_slot(hist_prefix, k, hvb);
     if (slot < slot_lo || slot >= slot_hi) continue;  // comm-overlap slot window
     const int chunk = hvb - hist_prefix[slot];
@@ -873,12 +910,19 @@ __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
     }
     const int fg_start = fg * feats_per_group;
     const int nf_group = min(feats_per_group, nfeat - fg_start);
-    const int lds_words = nf_group * stride * 2;
     const int hofs = (int)lds_half_words(nf_group * stride);
-    const int lds_padded = 2 * hofs;
 
-    for (int i = threadIdx.x; i < lds_padded; i += blockDim.x) lhist[i] = 0ull;
-    __syncthreads();
+    if (slot != live_slot || fg != live_fg) {
+      if (live_slot < 0) {
+        for (int i = threadIdx.x; i < 2 * hofs; i += blockDim.x) lhist[i] = 0ull;
+      } else {
+        __syncthreads();
+        hist_flush_slab(lhist, out, live_slot, live_fg, nfeat, stride, feats_per_group);
+      }
+      __syncthreads();
+      live_slot = slot;
+      live_fg = fg;
+    }
 
     const long long step = (long long)nb * blockDim.x;
     const bool vec4 = sizeof(BinT) == 1 && (nf_group & 3) == 0 && (nfeat & 3) == 0 &&
@@ -945,6 +989,8 @@ __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
           hist_add_row<BinT>(lhist, hofs, bins_c, gh_c, (long long)queue[i], false, nfeat,
                              fg_start, nf_group, stride, scale_g, scale_h);
       }
+      // the wave's next virtual block writes the queue from its start again
+      hist_wave_sync();
     } else {
       if (vec4) {
         for (; r + (HROWS - 1) * step < node.end; r += HROWS * step) {
@@ -971,34 +1017,33 @@ __global__ __launch_bounds__(BLOCK) void hist_device_kernel(
                            scale_g, scale_h);
       }
     }
+  }
+  if (live_slot >= 0) {
     __syncthreads();
-    unsigned long long* gout =
-        out + ((long long)slot * nfeat + fg_start) * (long long)stride * 2;
-    for (int i = threadIdx.x; i < lds_words; i += blockDim.x) {
-      const int pair = i >> 1;
-      const int idx = lds_pad_slot(pair) + ((i & 1) ? hofs : 0);
-      const unsigned long long v = lhist[idx];
-      if (v) atomicAdd(&gout[i], v);
-    }
-    __syncthreads();
+    hist_flush_slab(lhist, out, live_slot, live_fg, nfeat, stride, feats_per_group);
   }
 }
 
 // convert built slots (int64 acc -> f32 heap) and fill node sums from the
-// feature-0 bin range; one block per (slot, chunk of slots_total)
+// feature-0 bin range; one block per (slot, chunk of slots_total).
+// Every word of the level's acc[k * slots2] is written back as zero once it
+// is read, built slot or not (a communicator leaves sums in both slots of a
+// pair): the next level's atomics start from zero without a memset.
 __global__ __launch_bounds__(HIST_BLOCK) void convert_level_kernel(
-    const unsigned long long* __restrict__ acc, float* __restrict__ hist_f32,
+    unsigned long long* __restrict__ acc, float* __restrict__ hist_f32,
     const LevelNode* __restrict__ nodes, int k, long long slots2,
     const float* __restrict__ gh_max) {
   const double inv_g = (double)fmaxf(gh_max[0], 1e-30f) / 8589934592.0;
   const double inv_h = (double)fmaxf(gh_max[1], 1e-30f) / 8589934592.0;
   for (long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x; u < (long long)k * slots2;
        u += (long long)gridDim.x * blockDim.x) {
+    const unsigned long long v = acc[u];
+    if (v) acc[u] = 0ull;
     const int slot = (int)(u / slots2);
     if (!nodes[slot].build || nodes[slot].end <= nodes[slot].start) continue;
     const long long j = u - (long long)slot * slots2;
     const double inv = (j & 1) ? inv_h : inv_g;
-    hist_f32[u] = (float)((double)(long long)acc[u] * inv);
+    hist_f32[u] = (float)((double)(long long)v * inv);
   }
 }
 
@@ -2802,6 +2847,25 @@ void grow_make_level(torch::Tensor cur, torch::Tensor splits, torch::Tensor coun
                     (int)max_blocks, (int)filtered);
 }
 
+// The histogram grid when the caller names none (grid <= 0): a block flushes
+// its slab about once, so the grid is the number of flushes of a launch: the
+// blocks the device holds at once (CUs x blocks per CU, by LDS and by the
+// 2048 threads of a CU). Measured on the flagship, 1 / 2 / 3 / 6 times that
+// give 465 / 450 / 436 / 418 rounds/s (profiles/r16_hist_resident_slab.md):
+// what more blocks would even out at the tail costs less than their flushes.
+#define HIST_GRID_PER_RESIDENT 1
+
+static int hist_default_grid(int hist_block, size_t lds_bytes) {
+  int dev = 0, cus = 0;
+  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
+                  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) ==
+                      hipSuccess,
+              "histogram grid: cannot read the device's compute unit count");
+  const size_t by_lds = (size_t)160 * 1024 / std::max<size_t>(lds_bytes, 1);
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(by_lds, 2048 / hist_block));
+  return HIST_GRID_PER_RESIDENT * std::max(cus, 1) * per_cu;
+}
+
 // dispatch helper: BLOCK is a compile-time launch bound (256 grouped-slab,
 // 512 single full-feature slab); FILTER: see hist_device_kernel
 template <typename BinT, int FILTER>
@@ -2824,6 +2888,7 @@ static void launch_hist_device_impl(int grid, int hist_block, size_t lds_bytes, 
     return true;
   }();
   (void)lds_attr_set;
+  if (grid <= 0) grid = hist_default_grid(hist_block, lds_bytes);
   if (hist_block == 512) {
     hipLaunchKernelGGL((hist_device_kernel<BinT, 512, FILTER>), dim3(grid), dim3(512),
                        lds_bytes, stream, bins_c, gh_c, nodes, hist_prefix, work, acc, k, nfeat,
@@ -2910,8 +2975,9 @@ void grow_hist_level(torch::Tensor bins_c, torch::Tensor gh_c, torch::Tensor nod
 }
 
 // Fixed point -> float32 for the slots built from rows; with the parent
-// level's histograms given, every other slot as parent minus sibling.
-static void launch_convert_derive(hipStream_t stream, const unsigned long long* acc,
+// level's histograms given, every other slot as parent minus sibling. Leaves
+// acc[k * slots2] all zero (convert_level_kernel).
+static void launch_convert_derive(hipStream_t stream, unsigned long long* acc,
                                   float* level_hist, const float* parent_hist,
                                   const LevelNode* nodes, int k, long long slots2,
                                   const float* gh_max) {
@@ -2926,7 +2992,7 @@ static void launch_convert_derive(hipStream_t stream, const unsigned long long* 
 
 void grow_convert_level(torch::Tensor acc, torch::Tensor hist_f32, torch::Tensor nodes,
                         int64_t k, int64_t slots2, torch::Tensor gh_max) {
-  launch_convert_derive(current_stream(), (const unsigned long long*)acc.data_ptr<int64_t>(),
+  launch_convert_derive(current_stream(), (unsigned long long*)acc.data_ptr<int64_t>(),
                         hist_f32.data_ptr<float>(), nullptr,
                         (const LevelNode*)nodes.data_ptr<int>(), (int)k, slots2,
                         gh_max.data_ptr<float>());
@@ -3194,7 +3260,9 @@ void grow_tree_enqueue(
     float2* dst_gh = (float2*)(dpar ? gh1.data_ptr<float>() : gh0.data_ptr<float>());
     int* dst_rows = dpar ? rows1.data_ptr<int>() : rows0.data_ptr<int>();
 
-    hipMemsetAsync(acc.data_ptr<int64_t>(), 0, sizeof(int64_t) * (size_t)k * slots2, stream);
+    // `acc` is zero here: allocated so, and every level's convert launch
+    // leaves the words it read at zero. The hook gets its own memset: one
+    // that raised after its build has left sums behind for the next tree.
     unsigned long long* acc_ptr = (unsigned long long*)acc.data_ptr<int64_t>();
     if (hist_hook.is_none()) {
       launch_hist_level(u8, (int)hist_grid, (int)hist_block, lds_bytes, stream, src_bins, src_gh,
@@ -3202,6 +3270,7 @@ void grow_tree_enqueue(
                         (int)feats_per_group, gh_max.data_ptr<float>(), (int)rows_per_block, 0,
                         1 << 30, par_splits, (int)missing_bin, filter_deepest == 2);
     } else {
+      hipMemsetAsync(acc_ptr, 0, sizeof(int64_t) * (size_t)k * slots2, stream);
       hist_hook(d, level0 ? -1 : (int)par, filtered ? 1 : 0);
     }
     launch_convert_derive(

@@ -1505,7 +1505,10 @@ class _V1TreeState:
 
 
 
-_GROW_HIST_GRID = int(_os.environ.get("SMXGB_GROW_HIST_GRID", "1536"))
+# 0: the extension's own rule, a small multiple of the blocks the device
+# holds at once (hist_default_grid). A histogram block flushes its slab about
+# once, so this is the number of flushes of a launch.
+_GROW_HIST_GRID = int(_os.environ.get("SMXGB_GROW_HIST_GRID", "0"))
 _GROW_PART_GRID = int(_os.environ.get("SMXGB_GROW_PART_GRID", "4096"))
 # How a tree whose margins are updated by traversal builds its deepest
 # level's histograms: "filter" streams the ranges of the level above and
@@ -1596,7 +1599,11 @@ class DeviceGrower:
         # trees (multiclass class-trees, small data) need more blocks in
         # flight to fill 256 CUs — measured 141 -> 178 r/s on Covertype-
         # shape at 2048 vs 4096 (profiles/r02_optimization_log.md); the
-        # 12.5M-row flagship keeps 4096 (267 vs 257 at 2048).
+        # 12.5M-row flagship keeps 4096 (267 vs 257 at 2048). Since the
+        # histogram slab stays resident across a block's virtual blocks the
+        # value only balances the blocks: 4096 and 2048 measure level on the
+        # flagship, 4096 loses on Covertype-shape (164 vs 213 r/s,
+        # profiles/r16_hist_resident_slab.md).
         if _os.environ.get("SMXGB_ROWS_PER_BLOCK"):
             self.rows_per_block = _ROWS_PER_BLOCK
         else:
@@ -1614,7 +1621,8 @@ class DeviceGrower:
         self.splits = torch.empty((H, 6), dtype=torch.float32, device=device)
         self.counts = torch.zeros((H, 2), dtype=torch.int32, device=device)
         self.hist_f32 = torch.empty((H, self.slots2), dtype=torch.float32, device=device)
-        self.acc = torch.empty((max_k, self.slots2), dtype=torch.int64, device=device)
+        # zero from here on: each level's convert launch zeroes what it read
+        self.acc = torch.zeros((max_k, self.slots2), dtype=torch.int64, device=device)
         self.cands = torch.empty((max_k, f, 5), dtype=torch.float32, device=device)
         self.hp = [torch.empty((1 << d) + 1, dtype=torch.int32, device=device) for d in range(max_depth)]
         self.pp = [torch.empty((1 << d) + 1, dtype=torch.int32, device=device) for d in range(max_depth)]
