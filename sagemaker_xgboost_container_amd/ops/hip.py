@@ -210,6 +210,155 @@ def leaf_quantiles(pos, resid, n_leaves, alpha, weight=None, *, weight_max=None,
     return out
 
 
+# How ops/quantize.quantize builds the cuts and the bin matrix of a dense
+# float32 matrix on a ROCm device: "hip" runs csrc/smxgb_quantize.hip (cuts
+# by a radix select instead of a sort, bins by one kernel), "torch" keeps the
+# torch.sort / searchsorted code for A/B runs. Both give the same cuts and
+# bins, bit for bit. Weighted and distributed cuts and categorical matrices
+# are torch code under either value (the bins of the former two are not).
+# Read once at import; set_quantize_mode() switches it within a process.
+_QUANTIZE = _os.environ.get("SMXGB_QUANTIZE", "hip")
+_QUANTIZE_MODES = ("hip", "torch")
+
+
+def set_quantize_mode(mode):
+    """Select how dense matrices are quantized from now on ("hip" or
+    "torch"); returns the mode that was set before."""
+    global _QUANTIZE
+    if mode not in _QUANTIZE_MODES:
+        raise ValueError(f"SMXGB_QUANTIZE must be one of {list(_QUANTIZE_MODES)}, got {mode!r}")
+    previous = _QUANTIZE
+    _QUANTIZE = mode
+    return previous
+
+
+def quantize_mode():
+    return _QUANTIZE
+
+
+set_quantize_mode(_QUANTIZE)
+
+# Bytes of digit counters that make_cuts keeps at a time in passes 2 and 3: a
+# feature takes max_bin * 2048 * 4 of them, and the features go through the
+# passes in chunks that fit (at least one feature). Peak memory of cut
+# finding is X plus this, plus 8 KiB (pass 1) and max_bin floats per feature.
+QUANTIZE_COUNTER_BYTES = 256 << 20
+_QZ_DIGITS = 2048
+
+
+def make_cuts(X, max_bin=256):
+    """Cuts of a dense float32 [n][f] device matrix with NaN missing, by the
+    multi-target radix select of csrc/smxgb_quantize.hip: what
+    ops/quantize.make_cuts(X, max_bin) returns, bit for bit, without the
+    sort. Returns (cuts_flat, cut_ptr, nbins, has_missing) with cut_ptr on
+    the host as there.
+
+    The finite count of every feature is read back once after the first
+    pass (make_cuts reads it too): the target ranks are then built by the
+    reference's own torch expression, once per distinct count, so they are
+    the same numbers by construction. The sizes are read back at the end.
+    """
+    if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.is_contiguous()):
+        raise ValueError("X must be a contiguous 2-d float32 ROCm device tensor")
+    n, f = X.shape
+    max_bin = int(max_bin)
+    if n < 1 or f < 1:
+        raise ValueError("X must have rows and columns")
+    if not 1 <= max_bin <= MAX_HIST_STRIDE:
+        raise ValueError(f"max_bin must be in [1, {MAX_HIST_STRIDE}]")
+    dev = X.device
+    A, T = max_bin, max_bin - 1
+    Tp = max(T, 1)
+    i32 = dict(dtype=torch.int32, device=dev)
+    none = torch.empty(0, **i32)
+
+    counts1 = torch.zeros((f, _QZ_DIGITS), **i32)
+    _K.quantize_hist(X, 0, f, 1, none, none, A, counts1)
+    m = counts1.sum(1, dtype=torch.int32)
+    m_host = m.tolist()
+    sizes = sorted({v for v in m_host if v > 0})
+    if T > 0 and sizes:
+        ranks = torch.stack([
+            # ops/quantize._feature_cuts_sorted's positions, to the letter
+            torch.linspace(0, v - 1, max_bin + 1, device=dev)[1:-1].round().long() for v in sizes
+        ]).to(torch.int32).contiguous()
+    else:
+        ranks = torch.zeros((1, Tp), **i32)
+    row_of = {v: i for i, v in enumerate(sizes)}
+    ridx = torch.tensor([row_of.get(v, 0) for v in m_host], **i32)
+
+    per_feature = A * _QZ_DIGITS
+    chunk = max(1, min(QUANTIZE_COUNTER_BYTES // (4 * per_feature), ((1 << 31) - 1) // per_feature, f))
+    counts = torch.empty(chunk * per_feature, **i32)
+    cuts_pad = torch.empty((f, Tp), dtype=torch.float32, device=dev)
+    ncut = torch.empty(f, **i32)
+    for c0 in range(0, f, chunk):
+        fc = min(f, c0 + chunk) - c0
+        act = [torch.empty(fc * A, **i32) for _ in range(2)]
+        nact = [torch.empty(fc, **i32) for _ in range(2)]
+        state = torch.empty(3 * fc * Tp, **i32)
+        flag = torch.empty(fc, **i32)
+        mc, rc = m[c0:c0 + fc], ridx[c0:c0 + fc]
+        cnt = counts[: fc * per_feature]
+
+        def refine(p, table, src, dst):
+            _K.quantize_refine(p, table, act[src], nact[src], act[dst], nact[dst], A, max_bin,
+                               mc, ranks, rc, T, state, flag)
+
+        refine(1, counts1[c0:c0 + fc], 1, 0)
+        cnt.zero_()
+        _K.quantize_hist(X, c0, fc, 2, act[0], nact[0], A, cnt)
+        refine(2, cnt, 0, 1)
+        cnt.zero_()
+        _K.quantize_hist(X, c0, fc, 3, act[1], nact[1], A, cnt)
+        refine(3, cnt, 1, 0)
+        _K.quantize_final(act[0], nact[0], A, mc, flag, cuts_pad[c0:c0 + fc], Tp,
+                          ncut[c0:c0 + fc])
+    del counts, counts1
+
+    ptr_dev = torch.zeros(f + 1, dtype=torch.int64, device=dev)
+    ptr_dev[1:] = torch.cumsum(ncut, 0, dtype=torch.int64)
+    cut_ptr = ptr_dev.cpu()  # the one readback of sizes
+    cuts_flat = torch.empty(int(cut_ptr[-1]), dtype=torch.float32, device=dev)
+    if cuts_flat.numel():
+        _K.quantize_compact(cuts_pad, Tp, ncut, ptr_dev, cuts_flat)
+    nbins = ncut.to(torch.int64) + 1
+    return cuts_flat, cut_ptr, nbins, any(v < n for v in m_host)
+
+
+def bin_matrix(X, cuts, cut_ptr, stride):
+    """Bin matrix of a dense float32 [n][f] device matrix for given cuts:
+    bins[i][j] = number of feature j's cuts <= X[i][j], NaN -> stride - 1;
+    uint8, or int16 when stride > 256. One kernel launch per group of
+    features whose cuts fit the LDS together; nothing of X's size is
+    allocated but the result."""
+    if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.is_contiguous()):
+        raise ValueError("X must be a contiguous 2-d float32 ROCm device tensor")
+    n, f = X.shape
+    dev = X.device
+    stride = int(stride)
+    bins = torch.empty((n, f), dtype=torch.uint8 if stride <= 256 else torch.int16, device=dev)
+    if n == 0 or f == 0:
+        return bins
+    ptr = cut_ptr.cpu().to(torch.int64)
+    if ptr.numel() != f + 1:
+        raise ValueError("cut_ptr must have one entry per feature and one more")
+    ptr_dev = ptr.to(dev)
+    ptr = ptr.tolist()
+    cuts = cuts.to(device=dev, dtype=torch.float32).contiguous()
+    if ptr[0] != 0 or ptr[-1] != cuts.numel() or any(a > b for a, b in zip(ptr, ptr[1:])):
+        raise ValueError("cut_ptr must rise from 0 to the number of cuts")
+    room = int(_K.quantize_bin_lds_words())
+    g0 = 0
+    while g0 < f:
+        g1 = g0 + 1
+        while g1 < f and (g1 + 1 - g0) + 1 + (ptr[g1 + 1] - ptr[g0]) <= room:
+            g1 += 1
+        _K.quantize_bin(X, cuts, ptr_dev, g0, g1 - g0, ptr[g1] - ptr[g0], stride - 1, bins)
+        g0 = g1
+    return bins
+
+
 LAMBDARANK_CAP = int(_K.lambdarank_cap())
 LAMBDARANK_FLAG_NORM, LAMBDARANK_FLAG_SCORE, LAMBDARANK_FLAG_EXP_GAIN = 1, 2, 4
 

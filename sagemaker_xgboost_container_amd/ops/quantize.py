@@ -7,7 +7,9 @@ MI355X-first design: with 288 GB HBM3E per GPU the full feature matrix fits
 resident, so cuts come from an *exact* (optionally weighted) per-feature
 sort-based quantile pass on the GPU (torch.sort) instead of a streaming GK
 sketch — simpler, exact, and a one-time cost amortized over all boosting
-rounds. The quantized matrix uses a uniform per-feature bin stride so the
+rounds. On a ROCm device the unweighted single-process case finds the same
+cuts with a radix select instead of the sort, and every dense matrix is
+binned by one kernel (ops/csrc/smxgb_quantize.hip, see quantize()). The quantized matrix uses a uniform per-feature bin stride so the
 histogram kernels index ``slot = feature * stride + bin``; missing values
 (NaN) map to the last slot of the stride.
 
@@ -259,6 +261,21 @@ def _categorical_cuts(X, cat_cols, cuts, cut_ptr, nbins, comm, feature_names):
     return torch.cat(pieces), cut_ptr, nbins
 
 
+def _hip_quantizer(X, cat_cols):
+    """ops.hip when it quantizes X: a dense float32 matrix on a ROCm device
+    without a categorical column, unless SMXGB_QUANTIZE=torch (or
+    SMXGB_FORCE_TORCH_OPS=1) keeps the torch code below. A missing
+    extension is an ImportError, not a fallback."""
+    from . import _FORCE_TORCH
+
+    if (cat_cols or _FORCE_TORCH or not X.is_cuda or X.dtype != torch.float32
+            or X.dim() != 2 or 0 in X.shape):
+        return None
+    from . import hip
+
+    return hip if hip.quantize_mode() == "hip" else None
+
+
 def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=None, comm=None,
              is_cat=None, feature_names=None):
     """Quantize dense X (n, f) float32 with NaN missing into a QuantizedMatrix.
@@ -271,14 +288,27 @@ def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=
     is_cat: (f,) bools; a True column is categorical: bin = int(value), and
     its values must be missing or integers in [0, 254] (`feature_names`
     only names the column in that error).
+
+    On a ROCm device the bins come from the HIP binning kernel, and the cuts
+    of an unweighted single-process matrix from the HIP radix select
+    (ops/hip.make_cuts, the same cuts without the sort); weighted and
+    distributed cuts and categorical matrices stay on the torch code here.
     """
     n, f = X.shape
     cat_cols = [j for j, c in enumerate(is_cat) if c] if is_cat is not None else []
+    hipq = _hip_quantizer(X, cat_cols)
+    if hipq is not None:
+        X = X.contiguous()
+    has_missing = None
     if cuts is None:
         if comm is not None and comm.world_size > 1:
             cuts, cut_ptr, nbins = make_cuts_distributed(
                 X, max_bin=max_bin, sample_weight=sample_weight, comm=comm
             )
+        elif hipq is not None and sample_weight is None and 1 <= max_bin <= hipq.MAX_HIST_STRIDE:
+            # (a larger max_bin cannot train on this backend unless the data
+            # has few distinct values; the torch code keeps serving that)
+            cuts, cut_ptr, nbins, has_missing = hipq.make_cuts(X, max_bin)
         else:
             cuts, cut_ptr, nbins = make_cuts(X, max_bin=max_bin, sample_weight=sample_weight)
         if cat_cols:
@@ -286,7 +316,8 @@ def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=
                 X, cat_cols, cuts, cut_ptr, nbins, comm, feature_names
             )
 
-    has_missing = bool(torch.isnan(X).any().item())
+    if has_missing is None:  # the HIP cut finder counts the finite values anyway
+        has_missing = bool(torch.isnan(X).any().item())
     if comm is not None and comm.world_size > 1:
         # stride/missing-slot layout must agree across ranks
         flag = torch.tensor([1.0 if has_missing else 0.0], device=X.device)
@@ -296,9 +327,12 @@ def quantize(X, max_bin=256, sample_weight=None, cuts=None, cut_ptr=None, nbins=
     stride = max_nbins + (1 if has_missing else 0)
     dtype = torch.uint8 if stride <= 256 else torch.int16
 
-    bins = torch.empty((n, f), dtype=dtype, device=X.device)
+    if hipq is not None:
+        bins = hipq.bin_matrix(X, cuts, cut_ptr, stride)
+    else:
+        bins = torch.empty((n, f), dtype=dtype, device=X.device)
     cat_set = set(cat_cols)
-    for j in range(f):
+    for j in range(f if hipq is None else 0):
         col = X[:, j]
         cj = cuts[cut_ptr[j] : cut_ptr[j + 1]]
         if j in cat_set:

@@ -49,6 +49,7 @@ setup(
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantile.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_rank.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_rank_metric.hip",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/text_parsers.cpp",
             ],
             # headers shared by the sources: a change rebuilds the extension
