@@ -112,6 +112,20 @@ def _resolve_device(params):
     return torch.device("cpu")
 
 
+def _device_csr_quantize_ok(device, weight, comm, max_bin):
+    """Quantize the CSR training matrix with the HIP kernels of
+    ops/hip_sparse.quantize_csr? Unweighted single-process data on a ROCm
+    device, unless SMXGB_QUANTIZE=torch (or SMXGB_FORCE_TORCH_OPS=1) keeps
+    the host code of ops/sparse_ref.quantize_sparse."""
+    from ..ops import _FORCE_TORCH
+
+    if device.type != "cuda" or weight is not None or comm is not None or _FORCE_TORCH:
+        return False
+    from ..ops import hip
+
+    return hip.quantize_mode() == "hip" and 1 <= max_bin <= hip.MAX_HIST_STRIDE
+
+
 def _csr_tree_margin_fn(csr, device):
     """tree -> (n,) margin contribution over the rows of a scipy CSR matrix
     that stays sparse: the HIP traversal over an uploaded copy on a ROCm
@@ -387,17 +401,24 @@ def train(
     qm = None
     if params.get("booster", "gbtree") != "gblinear":
         if sparse_mode:
-            from ..ops.sparse_ref import quantize_sparse
+            if _device_csr_quantize_ok(device, weight, comm, max_bin):
+                # cut finding and binning run on the device and leave the
+                # matrix there (ops/hip_sparse.quantize_csr)
+                from ..ops import hip_sparse
 
-            qm = quantize_sparse(
-                Xcsr, max_bin=max_bin,
-                sample_weight=weight.cpu().numpy() if weight is not None else None,
-                comm=comm,
-            )
-            if device.type != "cpu":
-                # cut finding and binning stay on the host; the CSR arrays
-                # (never an n x f matrix) move to the device
-                qm = qm.to(device)
+                qm = hip_sparse.quantize_csr(Xcsr, max_bin=max_bin, device=device)
+            else:
+                from ..ops.sparse_ref import quantize_sparse
+
+                qm = quantize_sparse(
+                    Xcsr, max_bin=max_bin,
+                    sample_weight=weight.cpu().numpy() if weight is not None else None,
+                    comm=comm,
+                )
+                if device.type != "cpu":
+                    # weighted cuts (and SMXGB_QUANTIZE=torch) stay on the
+                    # host; the CSR arrays (never an n x f matrix) move over
+                    qm = qm.to(device)
         else:
             qm = quantize(
                 X, max_bin=max_bin, sample_weight=weight, comm=comm,

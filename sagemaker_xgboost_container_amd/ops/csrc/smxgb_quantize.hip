@@ -48,13 +48,13 @@
 // the midpoint (a + b) * 0.5 rounds like the reference's two operations
 #pragma clang fp contract(off)
 
+// qz_key, qz_value, qz_is_nan, qz_wave_add, qz_block_scan and the block shape
+#include "smxgb_quantize.h"
+
 #define CHECK_DEV(x, dt)                                                       \
   TORCH_CHECK_VALUE(x.is_cuda() && x.is_contiguous() && x.scalar_type() == dt, \
                     #x " must be a contiguous ROCm device tensor of the expected dtype")
 
-#define QZ_BLOCK 256
-#define QZ_WAVE 64
-#define QZ_WAVES (QZ_BLOCK / QZ_WAVE)
 #define QZ_ROWS 256                     // rows of a tile
 #define QZ_PER (QZ_ROWS / QZ_WAVE)      // consecutive rows of a lane
 #define QZ_FW 8                         // most features of a tile
@@ -62,51 +62,11 @@
 // reads are then 5 words apart) and 8 more between features
 #define QZ_TILE_STRIDE (QZ_ROWS + QZ_ROWS / QZ_PER + 8)
 #define QZ_TILE_WORDS (QZ_FW * QZ_TILE_STRIDE)
-#define QZ_DIGITS 2048                  // counters of a slot (pass 3 uses 1024)
-#define QZ_ELECT 2                      // leader elections per flush step
 #define QZ_LDS_BYTES (64 * 1024)
 #define QZ_MANY 1                       // flag: more than max_bin distinct values
 #define QZ_NAN_BITS 0x7fc00000u
 
 static hipStream_t quantize_stream() { return at::hip::getCurrentHIPStream().stream(); }
-
-__device__ __forceinline__ unsigned qz_key(unsigned b) {
-  if (b == 0x80000000u) b = 0u;  // -0.0 is the value +0.0
-  return b ^ ((b & 0x80000000u) ? 0xffffffffu : 0x80000000u);
-}
-
-__device__ __forceinline__ float qz_value(unsigned key) {
-  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-
-__device__ __forceinline__ bool qz_is_nan(unsigned b) { return (b & 0x7fffffffu) > 0x7f800000u; }
-
-// Adds cnt to tab[addr] for every lane with `pending`, all lanes of the wave
-// calling. Lanes that share the address of an elected leader are summed and
-// leave with one atomic.
-__device__ __forceinline__ void qz_wave_add(int* tab, int addr, int cnt, bool pending) {
-  const int lane = threadIdx.x & (QZ_WAVE - 1);
-  unsigned long long pend = __ballot(pending);
-  #pragma unroll
-  for (int round = 0; round < QZ_ELECT; ++round) {
-    if (pend == 0ull) break;  // uniform
-    const int leader = __ffsll((long long)pend) - 1;
-    const int la = __shfl(addr, leader, QZ_WAVE);
-    const bool match = pending && addr == la;
-    const unsigned long long mm = __ballot(match);
-    if (__popcll(mm) > 1) {  // uniform
-      int s = match ? cnt : 0;
-      #pragma unroll
-      for (int d = QZ_WAVE >> 1; d > 0; d >>= 1) s += __shfl_xor(s, d, QZ_WAVE);
-      if (lane == leader) atomicAdd(&tab[la], s);
-    } else if (lane == leader) {
-      atomicAdd(&tab[la], cnt);
-    }
-    pending = pending && !match;
-    pend &= ~mm;
-  }
-  if (pending) atomicAdd(&tab[addr], cnt);
-}
 
 // X: [n][f] row-major. The launch covers features [f0, f0 + fcount); counts,
 // active and nactive are indexed from f0. Block (x, y): the x-th group of fw
@@ -207,31 +167,6 @@ __global__ __launch_bounds__(QZ_BLOCK) void qz_hist_kernel(
       if (v != 0) atomicAdd(&counts[(long long)tf0 * QZ_DIGITS + i], v);
     }
   }
-}
-
-// Exclusive prefix sum of v over the block's threads; total: the block's sum.
-// s_w: QZ_WAVES words of LDS, free again on return.
-__device__ __forceinline__ int qz_block_scan(int v, int* s_w, int& total) {
-  const int lane = threadIdx.x & (QZ_WAVE - 1);
-  const int wave = threadIdx.x / QZ_WAVE;
-  int incl = v;
-  #pragma unroll
-  for (int d = 1; d < QZ_WAVE; d <<= 1) {
-    const int o = __shfl_up(incl, d, QZ_WAVE);
-    if (lane >= d) incl += o;
-  }
-  if (lane == QZ_WAVE - 1) s_w[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-  #pragma unroll
-  for (int w = 0; w < QZ_WAVES; ++w) {
-    const int x = s_w[w];
-    if (w < wave) base += x;
-    tot += x;
-  }
-  __syncthreads();
-  total = tot;
-  return base + incl - v;
 }
 
 // One workgroup per feature fl (all arrays indexed from the launch's first

@@ -216,13 +216,16 @@ def leaf_quantiles(pos, resid, n_leaves, alpha, weight=None, *, weight_max=None,
 # torch.sort / searchsorted code for A/B runs. Both give the same cuts and
 # bins, bit for bit. Weighted and distributed cuts and categorical matrices
 # are torch code under either value (the bins of the former two are not).
+# The same switch serves CSR training data: "hip" quantizes an unweighted
+# single-process matrix on the device (ops/hip_sparse.quantize_csr), "torch"
+# keeps ops/sparse_ref.quantize_sparse on the host.
 # Read once at import; set_quantize_mode() switches it within a process.
 _QUANTIZE = _os.environ.get("SMXGB_QUANTIZE", "hip")
 _QUANTIZE_MODES = ("hip", "torch")
 
 
 def set_quantize_mode(mode):
-    """Select how dense matrices are quantized from now on ("hip" or
+    """Select how training matrices are quantized from now on ("hip" or
     "torch"); returns the mode that was set before."""
     global _QUANTIZE
     if mode not in _QUANTIZE_MODES:

@@ -1,8 +1,8 @@
 """CDNA4 HIP backend for CSR data (MI355X sparse training and prediction).
 
 The device twin of ops/sparse_ref.py: a SparseQuantizedMatrix that lives on
-the GPU (`SparseQuantizedMatrix.to(device)`) trains without ever becoming an
-n x f bin matrix. Same backend interface as sparse_ref / hip
+the GPU (`quantize_csr`, or `SparseQuantizedMatrix.to(device)`) trains
+without ever becoming an n x f bin matrix. Same backend interface as sparse_ref / hip
 (make_tree_state, compute_scale, hist_to_float, find_splits,
 predict_tree_csr), so models/grower.py runs its per-level and lossguide
 loops unchanged. Kernels: csrc/smxgb_sparse.hip.
@@ -33,6 +33,11 @@ loops unchanged. Kernels: csrc/smxgb_sparse.hip.
   row accessor), bit-equal to its dense accessor on the NaN-densified rows.
   Interaction values over CSR are not implemented.
 
+* quantization: `quantize_csr` finds the cuts and bins the stored entries
+  of an unweighted scipy CSR matrix on the device (csrc/smxgb_quantize_csr.hip)
+  and returns the device matrix directly; weighted and distributed data are
+  quantized by sparse_ref.quantize_sparse on the host and moved with `.to`.
+
 There is no DeviceGrower for this layout: HistGrower.grow_path stays
 "per_level", which mirrors the device grower's float32 node arithmetic
 (MIRRORS_DEVICE_GROWER) so the trees equal the dense device path's.
@@ -61,6 +66,162 @@ leaf_quantiles = hip.leaf_quantiles
 # fewer rows than the dense kernels' 4096 to keep every CU issuing atomics.
 _HIST_ROWS_PER_BLOCK = 1024
 _PART_ROWS_PER_BLOCK = 4096  # one SPART_TILE
+
+
+# -- quantization ---------------------------------------------------------------
+# Longest feature segment (stored entries of one column) that quantize_csr
+# sorts in LDS; longer ones go through the radix select of hip.make_cuts.
+QUANTIZE_CSR_SORT_CAP = int(_K.quantize_csr_sort_cap())
+_QUANTIZE_CSR_WAVE_CAP = int(_K.quantize_csr_wave_cap())
+
+
+def _long_segment_cuts(keys, csc_ptr, heavy, m, max_bin, ranks, ridx, cuts_pad, ncut):
+    """Cuts of the features `heavy` (host ids, segments longer than the sort
+    cap) by hip.make_cuts' three radix passes over their key segments, in
+    chunks of features whose counters fit hip.QUANTIZE_COUNTER_BYTES."""
+    dev = keys.device
+    A, T = max_bin, max_bin - 1
+    Tp = max(T, 1)
+    i32 = dict(dtype=torch.int32, device=dev)
+    none = torch.empty(0, **i32)
+    per_feature = A * hip._QZ_DIGITS
+    chunk = max(1, min(hip.QUANTIZE_COUNTER_BYTES // (4 * per_feature),
+                       ((1 << 31) - 1) // per_feature, 65535, heavy.size))
+    counts = torch.empty(chunk * per_feature, **i32)
+    for c0 in range(0, heavy.size, chunk):
+        ids = heavy[c0:c0 + chunk]
+        fc = ids.size
+        ids32 = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        ids64 = ids32.long()
+        mc = torch.from_numpy(m[ids].astype(np.int32)).to(dev)
+        rc = ridx[ids64].contiguous()
+        max_len = int(m[ids].max())
+        act = [torch.empty(fc * A, **i32) for _ in range(2)]
+        nact = [torch.empty(fc, **i32) for _ in range(2)]
+        state = torch.empty(3 * fc * Tp, **i32)
+        flag = torch.empty(fc, **i32)
+        counts1 = torch.zeros(fc * hip._QZ_DIGITS, **i32)
+        cnt = counts[: fc * per_feature]
+
+        def refine(p, table, src, dst):
+            _K.quantize_refine(p, table, act[src], nact[src], act[dst], nact[dst], A, max_bin,
+                               mc, ranks, rc, T, state, flag)
+
+        _K.quantize_csr_hist(keys, csc_ptr, ids32, max_len, 1, none, none, A, counts1)
+        refine(1, counts1, 1, 0)
+        cnt.zero_()
+        _K.quantize_csr_hist(keys, csc_ptr, ids32, max_len, 2, act[0], nact[0], A, cnt)
+        refine(2, cnt, 0, 1)
+        cnt.zero_()
+        _K.quantize_csr_hist(keys, csc_ptr, ids32, max_len, 3, act[1], nact[1], A, cnt)
+        refine(3, cnt, 1, 0)
+        pad = torch.empty((fc, Tp), dtype=torch.float32, device=dev)
+        nc = torch.empty(fc, **i32)
+        _K.quantize_final(act[0], nact[0], A, mc, flag, pad, Tp, nc)
+        cuts_pad[ids64] = pad
+        ncut[ids64] = nc
+
+
+def quantize_csr(csr, max_bin=256, device="cuda"):
+    """The SparseQuantizedMatrix of an unweighted scipy CSR matrix, built on
+    the ROCm device: what sparse_ref.quantize_sparse(csr, max_bin).to(device)
+    returns, array for array and bit for bit, without its per-feature host
+    loop (kernels: csrc/smxgb_quantize_csr.hip).
+
+    The stored entries are counted per column and their keys scattered to a
+    CSC image; a feature of at most QUANTIZE_CSR_SORT_CAP entries is sorted in
+    LDS and cut there, a longer one goes through the radix select of
+    hip.make_cuts; one more kernel bins the entries in CSR order. The counts
+    are read back once: they size the job lists, and the target ranks come
+    from the reference's own linspace expression, once per distinct count.
+    Peak device memory is the CSR arrays, 4 bytes a stored entry for the
+    keys, the bins, f * max(max_bin - 1, 1) floats of padded cuts and at most
+    hip.QUANTIZE_COUNTER_BYTES; nothing of n x f size exists.
+
+    `csr` is not modified (unsorted column ids are sorted in a copy). A
+    stored NaN, or an empty matrix, returns the host result."""
+    from .sparse_ref import SparseQuantizedMatrix, quantize_sparse
+
+    max_bin = int(max_bin)
+    if not 1 <= max_bin <= hip.MAX_HIST_STRIDE:
+        raise ValueError(f"max_bin must be in [1, {hip.MAX_HIST_STRIDE}]")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("quantize_csr needs a ROCm device")
+    csr = csr.tocsr()
+    n, f = csr.shape
+    nnz = int(csr.indptr[-1]) if n else 0
+    if nnz >= 1 << 31:
+        raise ValueError("quantize_csr takes fewer than 2^31 stored entries")
+    if n == 0 or f == 0 or nnz == 0:
+        return quantize_sparse(csr, max_bin).to(dev)
+    if not csr.has_sorted_indices:
+        csr = csr.sorted_indices()
+    indptr = np.asarray(csr.indptr, dtype=np.int64)
+    if indptr.shape[0] != n + 1 or indptr[0] != 0 or csr.indices.shape[0] != nnz \
+            or csr.data.shape[0] != nnz or (np.diff(indptr) < 0).any():
+        raise ValueError("malformed CSR offsets")
+    i32 = dict(dtype=torch.int32, device=dev)
+    indices = torch.from_numpy(np.asarray(csr.indices, dtype=np.int32)).to(dev)
+    values = torch.from_numpy(np.asarray(csr.data, dtype=np.float32)).to(dev)
+
+    counts = torch.zeros(f + 1, **i32)
+    _K.quantize_csr_count(indices, values, counts)
+    counts_host = counts.cpu().numpy()  # the one readback the job lists need
+    if counts_host[f] & 2:
+        raise ValueError("CSR column ids out of range")
+    if counts_host[f] & 1:  # the host code owns the rule for a stored NaN
+        return quantize_sparse(csr, max_bin).to(dev)
+    m = counts_host[:f].astype(np.int64)
+    csc_ptr = torch.zeros(f + 1, **i32)
+    csc_ptr[1:] = torch.cumsum(counts[:f], 0, dtype=torch.int32)
+    keys = torch.empty(nnz, **i32)
+    _K.quantize_csr_scatter(indices, values, csc_ptr[:f].clone(), keys)
+
+    T = max_bin - 1
+    Tp = max(T, 1)
+    sizes = np.unique(m[m > max_bin])
+    if T > 0 and sizes.size:
+        ranks = torch.stack([
+            # ops/quantize._feature_cuts_sorted's positions, to the letter
+            torch.linspace(0, int(v) - 1, max_bin + 1)[1:-1].round().long() for v in sizes
+        ]).to(torch.int32).to(dev)
+        ridx = np.minimum(np.searchsorted(sizes, m), sizes.size - 1)
+    else:
+        ranks = torch.zeros((1, Tp), **i32)
+        ridx = np.zeros(f, dtype=np.int64)
+    ridx = torch.from_numpy(ridx.astype(np.int32)).to(dev)
+
+    cuts_pad = torch.empty((f, Tp), dtype=torch.float32, device=dev)
+    ncut = torch.zeros(f, **i32)  # a feature with fewer than two entries has no cut
+    below, P = 1, _QUANTIZE_CSR_WAVE_CAP
+    while P <= QUANTIZE_CSR_SORT_CAP:  # one job list per size class
+        jobs = np.flatnonzero((m > below) & (m <= P))
+        if jobs.size:
+            _K.quantize_csr_sort(keys, csc_ptr, torch.from_numpy(jobs.astype(np.int32)).to(dev),
+                                 P, max_bin, ranks, ridx, cuts_pad, Tp, ncut)
+        below, P = P, 2 * P
+    heavy = np.flatnonzero(m > QUANTIZE_CSR_SORT_CAP)
+    if heavy.size:
+        _long_segment_cuts(keys, csc_ptr, heavy, m, max_bin, ranks, ridx, cuts_pad, ncut)
+    del keys
+
+    cut_ptr = torch.zeros(f + 1, dtype=torch.int64, device=dev)
+    cut_ptr[1:] = torch.cumsum(ncut, 0, dtype=torch.int64)
+    total, widest = torch.stack([cut_ptr[-1], ncut.max().long()]).tolist()  # the sizes
+    cuts = torch.empty(total, dtype=torch.float32, device=dev)
+    if total:
+        _K.quantize_compact(cuts_pad, Tp, ncut, cut_ptr, cuts)
+    del cuts_pad
+    stride = widest + 2  # the widest feature's bins and the missing slot
+    bins = torch.empty(nnz, dtype=torch.uint8 if stride <= 256 else torch.int16, device=dev)
+    _K.quantize_csr_bin(indices, values, cuts, cut_ptr, bins)
+    return SparseQuantizedMatrix(
+        csr_bins=(torch.from_numpy(indptr).to(dev), indices, bins),
+        csc=(None, None, None),
+        cuts=cuts, cut_ptr=cut_ptr, nbins=ncut.to(torch.int64) + 1,
+        stride=stride, num_row=n, num_col=f,
+    )
 
 
 def _blocks(rows, per_block):

@@ -20,7 +20,10 @@ unchanged. This is the HOST backend. Its device twin is ops/hip_sparse.py:
 `SparseQuantizedMatrix.to(device)` moves the quantized CSR arrays to a
 ROCm device, where HIP kernels build the same histograms and partition by
 binary search in the sorted column ids instead of the CSC scratch column.
-quantize_sparse (cut finding, binning) serves both and runs on the host.
+quantize_sparse (cut finding, binning) runs on the host and defines the
+rule; on a ROCm device ops/hip_sparse.quantize_csr computes the same matrix
+with HIP kernels for unweighted single-process data, and quantize_sparse
+followed by `.to(device)` serves the rest (weights, a communicator).
 """
 import numpy as np
 import scipy.sparse as sp
@@ -100,8 +103,12 @@ class SparseQuantizedMatrix:
         A ROCm device gets the CSR arrays only (int64 offsets, int32 column
         ids, bins) plus cuts / nbins / cut_ptr: the device kernels find a
         row's split feature by binary search and need no CSC mirror, which
-        therefore stays on the host. On the CPU the CSC mirror is kept."""
+        therefore stays on the host. On the CPU the CSC mirror is kept. A
+        matrix that already lives on that ROCm device is returned as it is."""
         device = torch.device(device)
+        here = self.bin_data.device
+        if device.type != "cpu" and here.type == device.type and device.index in (None, here.index):
+            return self
         indptr, indices, bins = self._checked_sorted_csr()
         on_cpu = device.type == "cpu"
         idx_dtype = np.int64 if on_cpu else np.int32

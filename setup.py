@@ -50,12 +50,14 @@ setup(
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_rank.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_rank_metric.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize.hip",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize_csr.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/text_parsers.cpp",
             ],
             # headers shared by the sources: a change rebuilds the extension
             depends=[
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_cat.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_jobs.h",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_shap.h",
             ],
             extra_compile_args={
