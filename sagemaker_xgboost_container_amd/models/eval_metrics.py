@@ -2,7 +2,9 @@
 
 Computed with torch on whatever device the margins live on (GPU during
 training: predictions never leave HBM). AUC uses a sort-based exact
-computation. Names/directions match constants/xgb_constants.py.
+computation; on a ROCm device, binary auc and ndcg / map run HIP kernels
+instead (ops/hip.binary_auc, ops/hip.rank_metric). Names/directions match
+constants/xgb_constants.py.
 """
 import math
 import os
@@ -287,13 +289,34 @@ def _device_rank_metric(name, margin, y, objective, k, group_ptr, plans):
     return hip.rank_metric(plan, name, margin)[0]
 
 
+_AUC_PLAN = "auc"  # key of the auc plan in the caller's dict; ndcg / map use k
+
+
+def _device_auc(margin, y, weight, plans):
+    """auc through the HIP kernels (ops/hip.binary_auc): exact integer sums,
+    one scalar read back. `plans` caches the packed labels and weights for a
+    caller that scores the same data set every round; False marks a data set
+    the device path does not serve (labels outside {0, 1}), which stays on
+    auc()."""
+    from ..ops import hip
+
+    plan = plans.get(_AUC_PLAN) if plans is not None else None
+    if plan is None or (plan and plan["n"] != margin.numel()):
+        plan = hip.auc_plan(y, weight) or False
+        if plans is not None:
+            plans[_AUC_PLAN] = plan
+    if not plan:
+        return auc(margin, y, weight)
+    return hip.binary_auc(plan, margin)
+
+
 def evaluate(metric_name, margin, y, weight, objective, group_ptr=None, rank_plans=None):
     """Compute one named metric from raw margins via the objective transform.
 
     group_ptr: the (G+1,) query group boundaries of the scored data set, for
     ndcg / map; None looks the groups up through the objective. rank_plans: a
-    dict the caller keeps with the data set, in which the device path of
-    ndcg / map caches its work tables."""
+    dict the caller keeps with the data set, in which the device paths of
+    ndcg / map and of auc cache their work tables."""
     name = metric_name
     threshold = None
     if "@" in name:
@@ -345,6 +368,9 @@ def evaluate(metric_name, margin, y, weight, objective, group_ptr=None, rank_pla
     if name == "error":
         return error(pred, y, weight, threshold=0.5 if threshold is None else threshold)
     if name == "auc":
+        if (margin.is_cuda and margin.dim() == 1 and margin.numel() and y.numel() == margin.numel()
+                and os.environ.get("SMXGB_FORCE_TORCH_OPS") != "1"):
+            return _device_auc(margin, y, weight, rank_plans)
         return auc(pred, y, weight)
     if name == "aucpr":
         return aucpr(pred, y, weight)

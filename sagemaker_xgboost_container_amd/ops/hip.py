@@ -600,6 +600,97 @@ def rank_metric(plan, kind, margin):
     return float(mean), value
 
 
+AUC_CHUNK = int(_K.auc_chunk())
+_AUC_BAD_LABEL, _AUC_BAD_WEIGHT, _AUC_HAS_POS, _AUC_HAS_NEG = 1, 2, 4, 8
+
+
+def auc_plan(y, weight=None):
+    """What binary_auc keeps for one data set (csrc/smxgb_auc.hip), built
+    once: labels and weights do not change between rounds.
+
+    y: (n,) labels on a ROCm device; weight: (n,) weights there, or None.
+    One int64 per row holds the fixed-point weight round(w * 2^s) (1 without
+    weights) with the label in its low bit; 2^s is what
+    leaf_quantile_weight_scale(n, max w) gives, found on the device, so the
+    class sums P and N stay at or below 2^50. Two launches, then one
+    readback of the checks, P, N, s and the row count of label 1.
+
+    Returns None where the device path does not serve the data: a label
+    outside {0, 1}, a weight that is negative or not finite, or a class
+    whose weights all round to 0. Raises the ValueError of eval_metrics.auc
+    where a class has no weight at all."""
+    if not y.is_cuda or y.dim() != 1 or not (1 <= y.numel() < 2**31):
+        raise ValueError("y must be a 1-d ROCm device tensor of 1 to 2^31 - 1 rows")
+    n = y.numel()
+    dev = y.device
+    weighted = weight is not None and weight.numel() > 0
+    if weighted and (weight.shape != y.shape or weight.device != dev):
+        raise ValueError("weight must match y")
+    w = (weight.to(torch.float32).contiguous() if weighted
+         else torch.empty(0, dtype=torch.float32, device=dev))
+    i64 = dict(dtype=torch.int64, device=dev)
+    state = torch.zeros(6, **i64)
+    packed = torch.empty(n, **i64)
+    _K.auc_plan(y.to(torch.float32).contiguous(), w, state, packed)
+    flags, _, P, N, s, n_pos = state.tolist()  # the one synchronization
+    if flags & (_AUC_BAD_LABEL | _AUC_BAD_WEIGHT):
+        return None
+    if not (flags & _AUC_HAS_POS and flags & _AUC_HAS_NEG):
+        raise ValueError(torch_ref.AUC_ONE_CLASS_ERROR)
+    if P == 0 or N == 0:
+        return None
+    chunks = -(-n // AUC_CHUNK)
+    return {
+        "n": n, "P": P, "N": N, "s": s,
+        "n_pos": n_pos,
+        "packed": packed,
+        # scratch of a call; every call overwrites what it reads
+        "keys": torch.empty(n, **i64),
+        "gathered": torch.empty(n, **i64),
+        "prefix": torch.empty(n + 1, **i64),
+        "chunk_neg": torch.empty(chunks, **i64),
+        "chunk_base": torch.empty(chunks + 1, **i64),
+        "part": torch.empty(3 * chunks, **i64),
+    }
+
+
+def binary_auc(plan, margin):
+    """Binary ROC AUC of `margin` for the plan's labels and weights, on the
+    device; the rule and the float64 reference are torch_ref.binary_auc.
+    Returns a float, the one readback of the call: the keys kernel, a
+    torch.sort of the int64 keys and the scan kernels run back to back.
+
+    Every sum is an integer (the numerator in 128 bits), converted to
+    float64 once for the final division: the value does not depend on the
+    row order or on how the sort orders equal scores, and is the same bit
+    for bit from call to call. Unweighted, and weighted whenever every
+    w * 2^s is an integer, it is the quotient of the exact numerator and
+    denominator, each rounded once to float64; where both fit 53 bits that
+    is the reference's value bit for bit. For arbitrary float32 weights a
+    rounded weight is off by at most half a unit 2^-s, which moves each
+    class's normalised weights by at most n_class * 2^-s / (2 * W_class) in
+    total variation, so
+        |value - reference| <= 2^-s / 2 * (n_pos / P + n_neg / N) + 2^-50
+    with n_pos, n_neg the rows and P, N the weight sums of the two classes
+    as the plan holds them (plan["n_pos"], plan["n"] - plan["n_pos"], and
+    plan["P"], plan["N"] over 2^s); the last term covers the float64
+    roundings on both sides.
+
+    A NaN margin, an error by the rule, cannot raise here without a second
+    readback: it makes the value NaN."""
+    n = plan["n"]
+    if not margin.is_cuda or margin.dim() != 1 or margin.numel() != n:
+        raise ValueError("margin must be a 1-d ROCm device tensor with the plan's row count")
+    if margin.device != plan["packed"].device:
+        raise ValueError("margin must live on the plan's device")
+    _K.auc_keys(margin.to(torch.float32).contiguous(), plan["keys"])
+    out = torch.empty(1, dtype=torch.float64, device=margin.device)
+    _K.auc_scan(torch.sort(plan["keys"]).values, plan["packed"], plan["P"], plan["N"],
+                plan["gathered"], plan["prefix"], plan["chunk_neg"], plan["chunk_base"],
+                plan["part"], out)
+    return float(out)
+
+
 # Supported max_bin range of this backend, stated once. The split search
 # takes any number of bins (features above SPLIT_SCAN_BINS real bins go
 # through the wide split scan). The histogram kernels keep one feature's

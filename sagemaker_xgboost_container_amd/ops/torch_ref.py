@@ -1381,3 +1381,41 @@ def rank_metric(kind, margin, y, group_ptr=None, k=None):
             if n_pos:
                 out[g] = float((hit * np.cumsum(hit) / (pos + 1.0)).sum()) / n_pos
     return torch.from_numpy(out)
+
+
+# ---------------------------------------------------------------------------
+# Binary ROC AUC
+# ---------------------------------------------------------------------------
+AUC_ONE_CLASS_ERROR = "Check failed: !auc_error AUC: the dataset only contains pos or neg samples"
+
+
+def binary_auc(margin, y, weight=None):
+    """Exact tie-aware binary ROC AUC in float64, by a sort: the rule the
+    HIP kernels of csrc/smxgb_auc.hip follow in integers. Returns a float.
+
+    With p_i = w_i * y_i and n_i = w_i * (1 - y_i) (w_i = 1 without weights):
+        AUC = sum_i p_i * (N_<(s_i) + N_<=(s_i)) / (2 * P * N)
+    N_<(s) and N_<=(s) are the sums of n_j over the rows with s_j < s and
+    s_j <= s, P = sum p_i, N = sum n_i. Scores compare as float32 values,
+    -0.0 equal to +0.0. A NaN score makes the value NaN; P == 0 or N == 0
+    raises the error of eval_metrics.auc."""
+    import numpy as np
+
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+    s = as_np(margin).astype(np.float32).astype(np.float64).ravel() + 0.0  # -0.0 -> +0.0
+    lab = as_np(y).astype(np.float64).ravel()
+    w = np.ones_like(lab) if weight is None or len(weight) == 0 else as_np(weight).astype(np.float64).ravel()
+    if lab.size != s.size or w.size != s.size:
+        raise ValueError("y and weight must match margin")
+    p, neg = w * lab, w * (1.0 - lab)
+    P, N = float(p.sum()), float(neg.sum())
+    if P == 0.0 or N == 0.0:
+        raise ValueError(AUC_ONE_CLASS_ERROR)
+    if np.isnan(s).any():
+        return float("nan")
+    order = np.argsort(s, kind="stable")
+    ss = s[order]
+    below = np.concatenate([[0.0], np.cumsum(neg[order])])  # negative weight at sorted positions < q
+    n_lt = below[np.searchsorted(ss, ss, side="left")]
+    n_le = below[np.searchsorted(ss, ss, side="right")]
+    return float((p[order] * (n_lt + n_le)).sum()) / (2.0 * P * N)

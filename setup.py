@@ -51,6 +51,7 @@ setup(
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_rank_metric.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize_csr.hip",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_auc.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/text_parsers.cpp",
             ],
             # headers shared by the sources: a change rebuilds the extension
