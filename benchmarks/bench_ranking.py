@@ -1,13 +1,19 @@
 """Ranking on an MSLR-like set, two arms, each comparing two paths in one
 process.
 
-gradient: the sampled pair method (one random partner per document, a Python
-loop over the query groups) against the top-k LambdaRank kernels of
-csrc/smxgb_rank.hip.
+gradient: the sampled pair method (one drawn partner per document; on this
+data its kernel, lambdarank_mean_tile_kernel) against the top-k LambdaRank
+kernels of csrc/smxgb_rank.hip.
 eval: ndcg@10, ndcg and map through the per-group Python loop of
 models/eval_metrics.py (what SMXGB_FORCE_TORCH_OPS=1 runs) against the
 kernels of csrc/smxgb_rank_metric.hip, and a top-k training run that watches
 its training set with either.
+
+mean: the default pair method (lambdarank_pair_method=mean) at its defaults,
+the per-group Python loop (what SMXGB_FORCE_TORCH_OPS=1 runs, and all there
+was before the kernel) against lambdarank_mean_tile_kernel, on 20 000 groups
+of 50 documents and on 250 groups of 4 000: the loop pays per group, the
+kernel per document. Not part of --arm all.
 
     python benchmarks/bench_ranking.py [--arm all] [--rows 2400000] [--reps 3] [--rounds 3]
 
@@ -32,12 +38,12 @@ from sagemaker_xgboost_container_amd.models import eval_metrics, trainer  # noqa
 from sagemaker_xgboost_container_amd.models.objectives import create_objective  # noqa: E402
 
 
-def make_data(rows, features, seed):
+def make_data(rows, features, seed, sizes=None):
     """Seeded, MSLR-like: group sizes in [1, 1300] with a mean near 120
-    (lognormal), labels 0-4 that depend on a few features."""
+    (lognormal) unless given, labels 0-4 that depend on a few features."""
     rng = np.random.default_rng(seed)
-    sizes = []
-    left = rows
+    left = 0 if sizes else rows
+    sizes = list(sizes or [])
     while left > 0:
         m = int(min(left, np.clip(rng.lognormal(mean=4.45, sigma=0.8), 1, 1300)))
         sizes.append(m)
@@ -124,15 +130,50 @@ def eval_arm(args, dtrain, sizes, margin, yd):
     return out
 
 
+def mean_arm(args):
+    """ms per gradient call and rounds per second of a rank:ndcg run with
+    nothing else set, per-group loop against kernel."""
+    dev = torch.device("cuda")
+    out = {}
+    for shape, sizes in (("short_20000x50", [50] * 20000), ("long_250x4000", [4000] * 250)):
+        rows = sum(sizes)
+        X, y, _ = make_data(rows, args.mean_features, args.seed, sizes)
+        dtrain = DMatrix(X, label=y)
+        dtrain.set_group(sizes)
+        yd = torch.from_numpy(y).to(dev)
+        margin = yd * 0.5 + torch.randn(rows, device=dev, generator=torch.Generator(dev).manual_seed(1))
+        out[shape] = {}
+        for path, force in (("loop", "1"), ("kernel", "0")):
+            os.environ["SMXGB_FORCE_TORCH_OPS"] = force  # read by set_info, once per run
+            try:
+                objective = create_objective("rank:ndcg", {"objective": "rank:ndcg"})
+                objective.set_info(dtrain, dev)
+                objective.gradients(margin, yd, None)  # warm-up (plan, allocator)
+                ms = time_gradients(objective, margin, yd, args.reps)
+                sec = time_training({"objective": "rank:ndcg", "max_depth": 6, "eta": 0.3,
+                                     "device": "cuda"}, dtrain, args.rounds)
+            finally:
+                del os.environ["SMXGB_FORCE_TORCH_OPS"]
+            out[shape][path] = {
+                "grad_ms_median": statistics.median(ms), "grad_ms_min": min(ms),
+                "grad_ms_max": max(ms), "round_s": sec, "rounds_per_s": 1.0 / sec,
+            }
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arm", choices=["gradient", "eval", "all"], default="all")
+    ap.add_argument("--arm", choices=["gradient", "eval", "all", "mean"], default="all")
+    ap.add_argument("--mean-features", type=int, default=32)
     ap.add_argument("--rows", type=int, default=2_400_000)
     ap.add_argument("--features", type=int, default=136)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7)
     args = ap.parse_args()
+    if args.arm == "mean":
+        print(json.dumps({"mean": mean_arm(args)}))
+        return
     X, y, sizes = make_data(args.rows, args.features, args.seed)
     dtrain = DMatrix(X, label=y)
     dtrain.set_group(sizes)

@@ -12,12 +12,15 @@ constants/xgb_constants.CUSTOMER_ERRORS so algorithm_mode/train.py maps them
 to UserError (reference train.py:461-467 behavior).
 """
 import json
+import logging
 import math
 import os
 
 import torch
 
 from ..constants import xgb_constants as xgbc
+
+logger = logging.getLogger(__name__)
 
 
 def _fused_grad(name, margin, y, weight, scale_pos_weight=1.0):
@@ -376,7 +379,16 @@ class _RankObjective(Objective):
     """LambdaMART-style pairwise ranking base.
 
     Groups come from the DMatrix (qid / set_group); absent group info treats
-    the whole dataset as one query (xgboost behavior)."""
+    the whole dataset as one query (xgboost behavior).
+
+    lambdarank_pair_method=mean (the default) runs the sampled-pair kernel
+    of ops/csrc/smxgb_rank.hip where set_info finds that it can (a ROCm
+    device, integer labels, no group above its tile); the rule is then
+    ops/torch_ref.lambdarank_gradients with pair_method="mean". Its draws
+    are mixed from the `seed` parameter and a round counter that every
+    gradients call advances and set_info restarts: a training run resumed
+    from a checkpoint draws the pairs of round 0 again. Everywhere else the
+    per-group loop of `gradients` runs."""
 
     default_metric = "map"
 
@@ -385,7 +397,9 @@ class _RankObjective(Objective):
         self.group_ptr = None  # (G+1,) int64 boundaries
         p = self.params
         self.pair_method = str(p.get("lambdarank_pair_method", "mean"))
-        self._plan = None  # device work tables of the topk path, built once
+        self._plan = None  # device work tables of the kernels, built once
+        self._mean_loop = "set_info has not run"  # why mean runs the loop; None: the kernel
+        self._round = 0
         # Only parsed here: a Booster builds its objective to predict too,
         # and a loaded model may carry settings that training refuses
         # (_check_training_params, reached from set_info).
@@ -423,6 +437,65 @@ class _RankObjective(Objective):
             self.group_ptr = torch.as_tensor(ptr, dtype=torch.long, device=device)
         else:
             self.group_ptr = None
+        if self.pair_method == "mean":
+            self._round = 0
+            self._mean_loop = self._mean_loop_reason(dmatrix, device, group)
+            logger.debug("%s, lambdarank_pair_method=mean: %s", self.name,
+                         "device kernel" if self._mean_loop is None
+                         else f"per-group loop ({self._mean_loop})")
+
+    def _mean_loop_reason(self, dmatrix, device, group):
+        """Why lambdarank_pair_method=mean cannot run its kernel on this data
+        set, or None; checked once per training run."""
+        from ..ops import torch_ref
+
+        p = self.params
+        if torch.device(device).type != "cuda":
+            return "not a ROCm device"
+        if os.environ.get("SMXGB_FORCE_TORCH_OPS") == "1":
+            return "SMXGB_FORCE_TORCH_OPS=1"
+        if int(p.get("lambdarank_unbiased", 0) or 0):
+            return "lambdarank_unbiased"
+        from ..ops import hip as _hip  # raises if the extension is missing on GPU
+
+        self.num_pair = int(p.get("lambdarank_num_pair_per_sample", 1))
+        self.normalization = bool(int(p.get("lambdarank_normalization", 1)))
+        self.score_normalization = bool(int(p.get("lambdarank_score_normalization", 1)))
+        self.exp_gain = bool(int(p.get("ndcg_exp_gain", 1)))
+        self.seed = int(p.get("seed", 0) or 0)
+        if not (1 <= self.num_pair <= torch_ref.LAMBDARANK_MAX_K):
+            return "lambdarank_num_pair_per_sample outside [1, 4096]"
+        y = dmatrix.get_label()
+        largest = max(group, default=0) if group is not None else len(y)
+        if largest > _hip.LAMBDARANK_CAP:
+            return f"a group of more than {_hip.LAMBDARANK_CAP} documents"
+        if largest * self.num_pair > _hip.LAMBDARANK_MEAN_LIST:
+            return (f"largest group times lambdarank_num_pair_per_sample above "
+                    f"{_hip.LAMBDARANK_MEAN_LIST}")
+        try:
+            torch_ref.check_lambdarank_labels(torch.as_tensor(y), self.name)
+        except ValueError as e:
+            return str(e)
+        return None
+
+    def _mean_gradients(self, margin, y, weight):
+        from ..ops import hip as _hip
+        from ..ops import torch_ref
+
+        n = margin.shape[0]
+        if self._plan is None:
+            ptr = self.group_ptr if self.group_ptr is not None else [0, n]
+            self._plan = _hip.lambdarank_plan(ptr, self.num_pair, margin.device,
+                                              pair_method="mean")
+        flags = (
+            (_hip.LAMBDARANK_FLAG_NORM if self.normalization else 0)
+            | (_hip.LAMBDARANK_FLAG_SCORE if self.score_normalization else 0)
+            | (_hip.LAMBDARANK_FLAG_EXP_GAIN if self.exp_gain else 0)
+        )
+        self._round += 1
+        return _hip.lambdarank_mean_gradients(
+            self._plan, margin, y, weight, torch_ref.LAMBDARANK_KINDS[self.name], flags,
+            self.seed, self._round - 1)
 
     def _topk_gradients(self, margin, y, weight):
         """lambdarank_pair_method=topk: the HIP kernels on a ROCm device,
@@ -454,6 +527,8 @@ class _RankObjective(Objective):
     def gradients(self, margin, y, weight=None):
         if self.pair_method == "topk":
             return self._topk_gradients(margin, y, weight)
+        if self._mean_loop is None and margin.is_cuda:
+            return self._mean_gradients(margin, y, weight)
         n = margin.shape[0]
         device = margin.device
         grad = torch.zeros_like(margin)

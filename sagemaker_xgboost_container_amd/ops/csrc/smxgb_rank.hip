@@ -1,6 +1,8 @@
-// MI355X (gfx950 / CDNA4) kernels for the LambdaRank top-k pair gradient
-// (rank:pairwise, rank:ndcg, rank:map with lambdarank_pair_method=topk).
-// The rule and its float64 reference are ops/torch_ref.lambdarank_gradients.
+// MI355X (gfx950 / CDNA4) kernels for the LambdaRank pair gradients
+// (rank:pairwise, rank:ndcg, rank:map) with lambdarank_pair_method=topk and,
+// in lambdarank_mean_tile_kernel, which says how, with the sampled method
+// mean. The rule and its float64 reference are
+// ops/torch_ref.lambdarank_gradients. The top-k method:
 //
 // Per query group, documents are ranked by margin (descending, ties by row
 // index) and every position r < min(k, m) is paired with every position
@@ -50,6 +52,8 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <algorithm>
+
+#include "smxgb_rank_mix.h"
 
 typedef unsigned long long u64;
 
@@ -113,7 +117,12 @@ __device__ __forceinline__ int lr_label(float y) {
 //   u relevant:  h(v)/(v+1) - h(u)/(u+1) - (S(v) - S(u))
 //   v relevant:  (h(u)+1)/(u+1) - (h(v)+1)/(v+1) + (S(v) - S(u))
 // (the relevant documents strictly between lose, or gain, one hit each).
-template <int KIND>
+// The two quotients are float32 in the top-k kernels, where one of the two
+// positions is among the first k and the difference is not small. Between
+// two deep positions, which the sampled pairs reach, they agree in their
+// leading digits and a float32 quotient leaves the difference 1e-4 of its
+// value; WIDE forms them in float64.
+template <int KIND, bool WIDE = false>
 __device__ __forceinline__ void lr_pair(const LrDoc& a, const LrDoc& b, float grp,
                                         bool score_norm, bool exp_gain, float& lam, float& eta) {
   const float d = a.lab > b.lab ? a.s - b.s : b.s - a.s;  // s_hi - s_lo
@@ -126,10 +135,16 @@ __device__ __forceinline__ void lr_pair(const LrDoc& a, const LrDoc& b, float gr
     const LrDoc& u = a_first ? a : b;
     const LrDoc& v = a_first ? b : a;
     const int up = u.lab > 0 ? 0 : 1;  // v relevant: both hit counts grow by one
-    const float tu = (float)(u.hits + up) / (float)(u.pos + 1);
-    const float tv = (float)(v.hits + up) / (float)(v.pos + 1);
+    double tu, tv;
+    if (WIDE) {
+      tu = (double)(u.hits + up) / (double)(u.pos + 1);
+      tv = (double)(v.hits + up) / (double)(v.pos + 1);
+    } else {
+      tu = (double)((float)(u.hits + up) / (float)(u.pos + 1));
+      tv = (double)((float)(v.hits + up) / (float)(v.pos + 1));
+    }
     const double ds = v.S - u.S;
-    const double dap = u.lab > 0 ? ((double)tv - (double)tu) - ds : ((double)tu - (double)tv) + ds;
+    const double dap = u.lab > 0 ? (tv - tu) - ds : (tu - tv) + ds;
     delta = fabsf((float)dap) * grp;
   }
   // rho = 1/(1+exp(d)) and rho*(1-rho) from e = exp(-|d|) <= 1: neither
@@ -184,44 +199,86 @@ __device__ __forceinline__ void lr_block_absmax(float mg, float mh, bool bad, fl
 }
 
 // ---------------------------------------------------------------------------
-// Tile kernel
+// A tile: its LDS, the sort and the per-position tables, and the last phase.
+// Shared by the top-k tile kernel and the sampled (mean) tile kernel.
 // ---------------------------------------------------------------------------
-// tiles: int32 [T][2] (first group, group count). disc_prefix: float64
-// [>= min(k, LR_CAP) + 1], D[i] = sum_{p < i} 1/log2(p+2). scratch: float64
-// [n][3]. pmax: float32 [>= T][2], zero on entry.
 template <int KIND>
-__global__ __launch_bounds__(LR_BLOCK) void lambdarank_tile_kernel(
-    const float* __restrict__ margin, const float* __restrict__ label,
-    const float* __restrict__ weight, const int* __restrict__ group_ptr,
-    const int* __restrict__ tiles, const double* __restrict__ disc_prefix, int n, int n_groups,
-    int k, int flags, double* __restrict__ scratch, float* __restrict__ gh,
-    float* __restrict__ pmax) {
+struct LrTileLds {
   // the sorted keys, then the per-position tables in their place
-  __shared__ __align__(16) unsigned char s_raw[LR_CAP * 8];
+  __align__(16) unsigned char raw[LR_CAP * 8];
   // while the pairs run: S(p) by slot (rank:map) or disc(p) by position
   // (rank:ndcg); afterwards (every objective) the groups' factors
-  __shared__ double s_dbl[KIND != LR_PAIRWISE ? LR_CAP : LR_MAXG];
-  __shared__ int s_gstart[LR_MAXG + 1];
-  __shared__ float s_ginv[LR_MAXG];
-  __shared__ unsigned char s_gsn[LR_MAXG];
-  __shared__ int s_cnt[LR_WAVES][LR_LABELS];
-  __shared__ float s_red[LR_WAVES][2];
+  double dbl[KIND != LR_PAIRWISE ? LR_CAP : LR_MAXG];
+  int gstart[LR_MAXG + 1];
+  float ginv[LR_MAXG];
+  unsigned char gsn[LR_MAXG];
+  int cnt[LR_WAVES][LR_LABELS];
+  float red[LR_WAVES][2];
+};
+
+// what a workgroup knows of its tile once lr_tile_setup has run
+struct LrTile {
+  int base;  // first row
+  int N;     // documents
+  int ng;    // groups
+  bool bad;  // this thread saw a NaN margin
+};
+
+// group of tile slot i: the last one that starts at or before it
+__device__ __forceinline__ int lr_group_of(const int* s_gstart, int ng, int i) {
+  int lo = 0, hi = ng;  // s_gstart[lo] <= i < s_gstart[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (s_gstart[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+template <int KIND>
+__device__ __forceinline__ LrDoc lr_load_doc(const LrTileLds<KIND>& L, int slot, int gs) {
+  const float* s_score = (const float*)L.raw;
+  const unsigned short* s_hits = (const unsigned short*)(L.raw + LR_CAP * 4);
+  const unsigned char* s_lab = L.raw + LR_CAP * 6;
+  LrDoc d;
+  d.s = s_score[slot];
+  d.lab = s_lab[slot];
+  d.pos = slot - gs;
+  d.hits = KIND == LR_MAP ? (int)s_hits[slot] : 0;
+  d.S = KIND == LR_MAP ? L.dbl[slot] : (KIND == LR_NDCG ? L.dbl[slot - gs] : 0.0);
+  return d;
+}
+
+// Phases 1 and 2: sorts the tile and leaves the tables in L. idx[j]: the
+// row inside the tile of slot j * LR_BLOCK + t. False, for the whole
+// workgroup, when the tile is not one the host could have planned.
+// tiles: int32 [T][2] (first group, group count). disc_prefix: float64
+// [>= min(k, LR_CAP) + 1], D[i] = sum_{p < i} 1/log2(p+2).
+template <int KIND>
+__device__ __forceinline__ bool lr_tile_setup(
+    LrTileLds<KIND>& L, const float* __restrict__ margin, const float* __restrict__ label,
+    const int* __restrict__ group_ptr, const int* __restrict__ tiles,
+    const double* __restrict__ disc_prefix, int n, int n_groups, int k, int flags, LrTile& T,
+    int (&idx)[LR_SLOTS]) {
+  unsigned char* s_raw = L.raw;
+  int* s_gstart = L.gstart;
+  float* s_ginv = L.ginv;
+  unsigned char* s_gsn = L.gsn;
+  int (*s_cnt)[LR_LABELS] = L.cnt;
   u64* s_keys = (u64*)s_raw;
   float* s_score = (float*)s_raw;                                  // 16 KiB
   unsigned short* s_hits = (unsigned short*)(s_raw + LR_CAP * 4);  //  8 KiB
   unsigned char* s_lab = s_raw + LR_CAP * 6;                       //  4 KiB
-  double* s_S = s_dbl;
-  double* s_gfac = s_dbl;
+  double* s_S = L.dbl;
 
   const int t = threadIdx.x;
   const int lane = t & (LR_WAVE - 1);
   const int w = t / LR_WAVE;
   const int g0 = tiles[2 * blockIdx.x];
   const int ng = tiles[2 * blockIdx.x + 1];
-  if (g0 < 0 || ng < 1 || ng > LR_MAXG || g0 > n_groups - ng) return;  // uniform
+  if (g0 < 0 || ng < 1 || ng > LR_MAXG || g0 > n_groups - ng) return false;  // uniform
   const int base = group_ptr[g0];
   const int N = group_ptr[g0 + ng] - base;
-  if (base < 0 || N < 0 || N > LR_CAP || base > n - N) return;  // uniform
+  if (base < 0 || N < 0 || N > LR_CAP || base > n - N) return false;  // uniform
   const bool exp_gain = (flags & LR_F_EXP) != 0;
 
   for (int i = t; i <= ng; i += LR_BLOCK) {
@@ -230,15 +287,7 @@ __global__ __launch_bounds__(LR_BLOCK) void lambdarank_tile_kernel(
   }
   __syncthreads();
 
-  // group of tile slot i: the last one that starts at or before it
-  auto group_of = [&](int i) {
-    int lo = 0, hi = ng;  // s_gstart[lo] <= i < s_gstart[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_gstart[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-  };
+  auto group_of = [&](int i) { return lr_group_of(s_gstart, ng, i); };
 
   // -- 1. keys and one bitonic sort over the tile ---------------------------
   int P = 2;
@@ -274,7 +323,6 @@ __global__ __launch_bounds__(LR_BLOCK) void lambdarank_tile_kernel(
 
   // -- keys -> tables, in place: thread t owns slots t, t + 256, ... --------
   u64 kreg[LR_SLOTS];
-  int idx[LR_SLOTS];
   #pragma unroll
   for (int j = 0; j < LR_SLOTS; ++j) {
     const int slot = j * LR_BLOCK + t;
@@ -366,16 +414,87 @@ __global__ __launch_bounds__(LR_BLOCK) void lambdarank_tile_kernel(
     }
   }
   __syncthreads();
+  T.base = base;
+  T.N = N;
+  T.ng = ng;
+  T.bad = bad;
+  return true;
+}
 
-  auto load_doc = [&](int slot, int gs) {
-    LrDoc d;
-    d.s = s_score[slot];
-    d.lab = s_lab[slot];
-    d.pos = slot - gs;
-    d.hits = KIND == LR_MAP ? (int)s_hits[slot] : 0;
-    d.S = KIND == LR_MAP ? s_S[slot] : (KIND == LR_NDCG ? s_S[slot - gs] : 0.0);
-    return d;
-  };
+// Phase 4: group normalisation, clamp, weight, scatter to the rows and the
+// workgroup's |g|, |h| maxima. scratch holds the tile's unnormalised (g, h,
+// half-lambda) by sorted position; the barrier in front orders it, and the
+// last reads of the tables, before the factors take their place in L.dbl.
+template <int KIND>
+__device__ __forceinline__ void lr_tile_finish(
+    LrTileLds<KIND>& L, const LrTile& T, const int (&idx)[LR_SLOTS],
+    const float* __restrict__ weight, int flags, const double* __restrict__ scratch,
+    float* __restrict__ gh, float* __restrict__ pmax) {
+  const int t = threadIdx.x;
+  const int lane = t & (LR_WAVE - 1);
+  const int w = t / LR_WAVE;
+  const int base = T.base, N = T.N, ng = T.ng;
+  const int* s_gstart = L.gstart;
+  double* s_gfac = L.dbl;
+  __syncthreads();  // S(p) is dead from here: L.dbl takes the factors
+  for (int gi = w; gi < ng; gi += LR_WAVES) {
+    const int gs = s_gstart[gi];
+    const int m = s_gstart[gi + 1] - gs;
+    double sum = 0.0;
+    for (int p = lane; p < m; p += LR_WAVE) sum += scratch[(long long)(base + gs + p) * 3 + 2];
+    sum = lr_wave_sum(sum);
+    if (lane == 0) s_gfac[gi] = lr_norm_factor(sum, flags);
+  }
+  __syncthreads();
+  float mg = 0.0f, mh = 0.0f;
+  #pragma unroll
+  for (int j = 0; j < LR_SLOTS; ++j) {
+    const int slot = j * LR_BLOCK + t;
+    if (slot < N) {
+      const double fac = s_gfac[lr_group_of(s_gstart, ng, slot)];
+      const double* in = scratch + (long long)(base + slot) * 3;
+      const long long row = (long long)base + idx[j];
+      const double wt = weight != nullptr ? (double)weight[row] : 1.0;
+      double h = in[1] * fac;
+      h = h < 1e-16 ? 1e-16 : h;
+      const float gf = (float)(in[0] * fac * wt);
+      const float hf = (float)(h * wt);
+      gh[row * 2] = gf;
+      gh[row * 2 + 1] = hf;
+      mg = fmaxf(mg, fabsf(gf));
+      mh = fmaxf(mh, fabsf(hf));
+    }
+  }
+  lr_block_absmax(mg, mh, T.bad, L.red, pmax + 2 * (long long)blockIdx.x);
+}
+
+// ---------------------------------------------------------------------------
+// Top-k tile kernel
+// ---------------------------------------------------------------------------
+// scratch: float64 [n][3]. pmax: float32 [>= T][2], zero on entry.
+template <int KIND>
+__global__ __launch_bounds__(LR_BLOCK) void lambdarank_tile_kernel(
+    const float* __restrict__ margin, const float* __restrict__ label,
+    const float* __restrict__ weight, const int* __restrict__ group_ptr,
+    const int* __restrict__ tiles, const double* __restrict__ disc_prefix, int n, int n_groups,
+    int k, int flags, double* __restrict__ scratch, float* __restrict__ gh,
+    float* __restrict__ pmax) {
+  __shared__ LrTileLds<KIND> L;
+  LrTile T;
+  int idx[LR_SLOTS];
+  if (!lr_tile_setup<KIND>(L, margin, label, group_ptr, tiles, disc_prefix, n, n_groups, k,
+                           flags, T, idx))
+    return;
+  const int t = threadIdx.x;
+  const int lane = t & (LR_WAVE - 1);
+  const int w = t / LR_WAVE;
+  const int base = T.base, N = T.N, ng = T.ng;
+  const bool exp_gain = (flags & LR_F_EXP) != 0;
+  const int* s_gstart = L.gstart;
+  const float* s_ginv = L.ginv;
+  const unsigned char* s_gsn = L.gsn;
+  auto group_of = [&](int i) { return lr_group_of(s_gstart, ng, i); };
+  auto load_doc = [&](int slot, int gs) { return lr_load_doc<KIND>(L, slot, gs); };
 
   // -- 3a. every document against the top-k positions of its group ---------
   #pragma unroll 1
@@ -434,38 +553,208 @@ __global__ __launch_bounds__(LR_BLOCK) void lambdarank_tile_kernel(
       }
     }
   }
-  __syncthreads();  // S(p) is dead from here: s_dbl takes the factors
 
   // -- 4. group normalisation, clamp, weight, scatter -----------------------
-  for (int gi = w; gi < ng; gi += LR_WAVES) {
-    const int gs = s_gstart[gi];
-    const int m = s_gstart[gi + 1] - gs;
-    double sum = 0.0;
-    for (int p = lane; p < m; p += LR_WAVE) sum += scratch[(long long)(base + gs + p) * 3 + 2];
-    sum = lr_wave_sum(sum);
-    if (lane == 0) s_gfac[gi] = lr_norm_factor(sum, flags);
-  }
-  __syncthreads();
-  float mg = 0.0f, mh = 0.0f;
+  lr_tile_finish<KIND>(L, T, idx, weight, flags, scratch, gh, pmax);
+}
+
+// ---------------------------------------------------------------------------
+// Sampled (mean) tile kernel: lambdarank_pair_method=mean
+// ---------------------------------------------------------------------------
+// Every document draws P partners inside its group (smxgb_rank_mix.h) and a
+// pair is kept where the labels differ. The drawer's side of a pair is easy:
+// the thread that owns the document adds its P terms in order of t. The
+// partner's side must reach another thread's document without a float
+// atomic and in one fixed order. The draws are therefore turned round in LDS
+// with integers only:
+//   A  every kept draw (a, t) -> b adds 1 to count[b]          (int atomic)
+//   B  a workgroup scan turns the counts into list offsets
+//   C  every kept draw drops its id a * P + t into b's list through b's
+//      cursor (int atomic); the drawer's own term is computed on the way and
+//      its float64 sums go to the scratch row of its sorted position
+//   D  the owner of b sorts b's short list by id (expected length: P times
+//      the share of kept draws), recomputes those terms from the tables in
+//      that order and adds them to the same scratch row
+// a is the row inside the tile, so ids of one group rise with (row, t)
+// whatever tile the group was packed into, and with them the order of every
+// sum. lr_pair gives the same bits from either end of a pair, so recomputing
+// a term costs one table lookup more than storing it and saves 8 bytes of
+// LDS per draw. Then phase 4 as in the top-k kernel.
+//
+// LDS budget (gfx950: 160 KiB per workgroup), rank:ndcg / rank:map:
+//   tables (LrTileLds)              32 KiB + 32 KiB + 3.6 KiB
+//   slot of each row (u16)           8 KiB
+//   counts -> offsets -> cursors    16 KiB + 16 B
+//   lists, LR_MLIST ids (u16)       32 KiB          total 123.6 KiB
+// The host keeps a tile's documents times P at or below LR_MLIST
+// (ops/hip.lambdarank_plan lowers tile_docs), which also makes every id fit
+// 16 bits.
+#define LR_MLIST 16384
+
+template <int KIND>
+__global__ __launch_bounds__(LR_BLOCK) void lambdarank_mean_tile_kernel(
+    const float* __restrict__ margin, const float* __restrict__ label,
+    const float* __restrict__ weight, const int* __restrict__ group_ptr,
+    const int* __restrict__ tiles, const double* __restrict__ disc_prefix, int n, int n_groups,
+    int P, int flags, u64 seed, u64 round, double* __restrict__ scratch,
+    float* __restrict__ gh, float* __restrict__ pmax) {
+  __shared__ LrTileLds<KIND> L;
+  __shared__ unsigned short s_slot[LR_CAP];  // sorted slot of each row of the tile
+  __shared__ int s_cur[LR_CAP];              // A: counts, B: offsets, C: cursors -> list ends
+  __shared__ int s_wsum[LR_WAVES];
+  __shared__ unsigned short s_list[LR_MLIST];
+  LrTile T;
+  int idx[LR_SLOTS];
+  // k = LR_CAP: the IDCG of rank:ndcg runs over the whole group
+  if (!lr_tile_setup<KIND>(L, margin, label, group_ptr, tiles, disc_prefix, n, n_groups, LR_CAP,
+                           flags, T, idx))
+    return;
+  const int t = threadIdx.x;
+  const int lane = t & (LR_WAVE - 1);
+  const int w = t / LR_WAVE;
+  const int base = T.base, N = T.N, ng = T.ng;
+  if (P < 1 || (long long)N * P > LR_MLIST) return;  // uniform; the host checks it too
+  const bool exp_gain = (flags & LR_F_EXP) != 0;
+  const int* s_gstart = L.gstart;
+  const unsigned char* s_lab = L.raw + LR_CAP * 6;
+  const u64 key = lr_mix_key(seed, round);
+
   #pragma unroll
   for (int j = 0; j < LR_SLOTS; ++j) {
     const int slot = j * LR_BLOCK + t;
     if (slot < N) {
-      const double fac = s_gfac[group_of(slot)];
-      const double* in = scratch + (long long)(base + slot) * 3;
-      const long long row = (long long)base + idx[j];
-      const double wt = weight != nullptr ? (double)weight[row] : 1.0;
-      double h = in[1] * fac;
-      h = h < 1e-16 ? 1e-16 : h;
-      const float gf = (float)(in[0] * fac * wt);
-      const float hf = (float)(h * wt);
-      gh[row * 2] = gf;
-      gh[row * 2 + 1] = hf;
-      mg = fmaxf(mg, fabsf(gf));
-      mh = fmaxf(mh, fabsf(hf));
+      s_slot[idx[j]] = (unsigned short)slot;
+      s_cur[slot] = 0;
     }
   }
-  lr_block_absmax(mg, mh, bad, s_red, pmax + 2 * (long long)blockIdx.x);
+  __syncthreads();
+
+  // slot of the partner that draw t of the document at `row` of group
+  // [gs, gs + m) picks, m >= 2
+  auto partner_slot = [&](int row, int gs, int m, int tt) {
+    const u64 r = lr_mix(key, (u64)(base + row), (u64)tt);
+    const int b = (int)lr_mix_partner(r, (uint32_t)(row - gs), (uint32_t)m);
+    return (int)s_slot[gs + b];
+  };
+
+  // -- A. incoming kept draws per document, counted by sorted slot ----------
+  #pragma unroll 1
+  for (int j = 0; j < LR_SLOTS; ++j) {
+    const int slot = j * LR_BLOCK + t;
+    if (slot >= N) continue;
+    const int gi = lr_group_of(s_gstart, ng, slot);
+    const int gs = s_gstart[gi];
+    const int m = s_gstart[gi + 1] - gs;
+    if (m < 2) continue;
+    const int lab = s_lab[slot];
+    for (int tt = 0; tt < P; ++tt) {
+      const int sb = partner_slot(idx[j], gs, m, tt);
+      if ((int)s_lab[sb] != lab) atomicAdd(&s_cur[sb], 1);
+    }
+  }
+  __syncthreads();
+
+  // -- B. exclusive scan of the counts: thread t owns LR_SLOTS neighbours ---
+  {
+    int c[LR_SLOTS];
+    int sum = 0;
+    #pragma unroll
+    for (int q = 0; q < LR_SLOTS; ++q) {
+      const int i = t * LR_SLOTS + q;
+      c[q] = i < N ? s_cur[i] : 0;
+      sum += c[q];
+    }
+    int inc = sum;
+    #pragma unroll
+    for (int d = 1; d < LR_WAVE; d <<= 1) {
+      const int o = __shfl_up(inc, d, LR_WAVE);
+      if (lane >= d) inc += o;
+    }
+    if (lane == LR_WAVE - 1) s_wsum[w] = inc;
+    __syncthreads();
+    int off = inc - sum;
+    for (int i = 0; i < w; ++i) off += s_wsum[i];
+    #pragma unroll
+    for (int q = 0; q < LR_SLOTS; ++q) {
+      const int i = t * LR_SLOTS + q;
+      if (i < N) s_cur[i] = off;
+      off += c[q];
+    }
+  }
+  __syncthreads();
+
+  // -- C. the drawer's side, and the draw's id into the partner's list ------
+  #pragma unroll 1
+  for (int j = 0; j < LR_SLOTS; ++j) {
+    const int slot = j * LR_BLOCK + t;
+    if (slot >= N) continue;
+    const int gi = lr_group_of(s_gstart, ng, slot);
+    const int gs = s_gstart[gi];
+    const int m = s_gstart[gi + 1] - gs;
+    double g = 0.0, h = 0.0, half = 0.0;
+    if (m >= 2) {
+      const float grp = L.ginv[gi];
+      const bool sn = L.gsn[gi] != 0;
+      const LrDoc me = lr_load_doc<KIND>(L, slot, gs);
+      for (int tt = 0; tt < P; ++tt) {
+        const int sb = partner_slot(idx[j], gs, m, tt);
+        const LrDoc ot = lr_load_doc<KIND>(L, sb, gs);
+        if (ot.lab == me.lab) continue;
+        float lam, eta;
+        lr_pair<KIND, true>(me, ot, grp, sn, exp_gain, lam, eta);
+        g += me.lab > ot.lab ? -(double)lam : (double)lam;
+        h += (double)eta;
+        half += (double)lam;  // every kept draw once: the drawer counts it
+        const int at = atomicAdd(&s_cur[sb], 1);
+        if (at < LR_MLIST) s_list[at] = (unsigned short)(idx[j] * P + tt);  // always: N * P fits
+      }
+    }
+    double* out = scratch + (long long)(base + slot) * 3;
+    out[0] = g;
+    out[1] = h;
+    out[2] = half;
+  }
+  __syncthreads();
+
+  // -- D. the partner's side: the list of slot i is [s_cur[i-1], s_cur[i]) --
+  #pragma unroll 1
+  for (int j = 0; j < LR_SLOTS; ++j) {
+    const int slot = j * LR_BLOCK + t;
+    if (slot >= N) continue;
+    const int lo = slot > 0 ? s_cur[slot - 1] : 0;
+    int hi = s_cur[slot];
+    hi = hi < LR_MLIST ? hi : LR_MLIST;
+    if (hi <= lo) continue;
+    for (int i = lo + 1; i < hi; ++i) {  // insertion sort: the list is short
+      const unsigned short v = s_list[i];
+      int q = i - 1;
+      while (q >= lo && s_list[q] > v) {
+        s_list[q + 1] = s_list[q];
+        --q;
+      }
+      s_list[q + 1] = v;
+    }
+    const int gi = lr_group_of(s_gstart, ng, slot);
+    const int gs = s_gstart[gi];
+    const float grp = L.ginv[gi];
+    const bool sn = L.gsn[gi] != 0;
+    const LrDoc me = lr_load_doc<KIND>(L, slot, gs);
+    double* out = scratch + (long long)(base + slot) * 3;
+    double g = out[0], h = out[1];
+    for (int i = lo; i < hi; ++i) {
+      const int row = (int)s_list[i] / P;  // the drawer
+      if (row >= N) continue;              // cannot happen: ids are below N * P
+      const LrDoc ot = lr_load_doc<KIND>(L, (int)s_slot[row], gs);
+      float lam, eta;
+      lr_pair<KIND, true>(me, ot, grp, sn, exp_gain, lam, eta);
+      g += me.lab > ot.lab ? -(double)lam : (double)lam;
+      h += (double)eta;
+    }
+    out[0] = g;
+    out[1] = h;
+  }
+
+  lr_tile_finish<KIND>(L, T, idx, weight, flags, scratch, gh, pmax);
 }
 
 // ---------------------------------------------------------------------------
@@ -749,6 +1038,7 @@ int64_t lambdarank_cap() { return LR_CAP; }
 int64_t lambdarank_max_groups() { return LR_MAXG; }
 int64_t lambdarank_stream_chunk() { return LR_SCHUNK; }
 int64_t lambdarank_finish_grid() { return LR_FINISH_GRID; }
+int64_t lambdarank_mean_list() { return LR_MLIST; }
 
 // weight may be empty. tiles: [T, 2]; pmax: zeroed, at least T rows.
 void lambdarank_tile(torch::Tensor margin, torch::Tensor label, torch::Tensor weight,
@@ -789,6 +1079,53 @@ void lambdarank_tile(torch::Tensor margin, torch::Tensor label, torch::Tensor we
   else LR_LAUNCH_TILE(LR_PAIRWISE);
 #undef LR_LAUNCH_TILE
   rank_check_launch("lambdarank_tile_kernel");
+}
+
+// lambdarank_pair_method=mean over every tile; no group may be larger than a
+// tile. P: draws per document. disc_prefix: LR_CAP + 1 entries. Otherwise as
+// lambdarank_tile.
+void lambdarank_mean_tile(torch::Tensor margin, torch::Tensor label, torch::Tensor weight,
+                          torch::Tensor group_ptr, torch::Tensor tiles, torch::Tensor disc_prefix,
+                          int64_t P, int64_t tile_docs, int64_t kind, int64_t flags, int64_t seed,
+                          int64_t round, torch::Tensor scratch, torch::Tensor gh,
+                          torch::Tensor pmax) {
+  CHECK_DEV(margin, torch::kFloat32);
+  CHECK_DEV(label, torch::kFloat32);
+  CHECK_DEV(weight, torch::kFloat32);
+  CHECK_DEV(group_ptr, torch::kInt32);
+  CHECK_DEV(tiles, torch::kInt32);
+  CHECK_DEV(disc_prefix, torch::kFloat64);
+  CHECK_DEV(scratch, torch::kFloat64);
+  CHECK_DEV(gh, torch::kFloat32);
+  CHECK_DEV(pmax, torch::kFloat32);
+  rank_check_common(P, kind, flags);
+  const int64_t n = margin.numel();
+  const int64_t T = tiles.numel() / 2;
+  TORCH_CHECK_VALUE(n >= 1 && n < (1ll << 31), "row count must be in [1, 2^31)");
+  TORCH_CHECK_VALUE(label.numel() == n && gh.numel() == 2 * n && scratch.numel() == 3 * n,
+                    "label, gh and scratch must match margin");
+  TORCH_CHECK_VALUE(weight.numel() == 0 || weight.numel() == n, "weight must match margin");
+  TORCH_CHECK_VALUE(group_ptr.numel() >= 2 && tiles.numel() == 2 * T && T >= 1 &&
+                        pmax.numel() >= 2 * T,
+                    "tiles must be [T, 2] with a pmax row per tile");
+  TORCH_CHECK_VALUE(disc_prefix.numel() >= LR_CAP + 1, "disc_prefix must hold cap + 1 entries");
+  TORCH_CHECK_VALUE(tile_docs >= 1 && tile_docs * P <= LR_MLIST,
+                    "a tile's documents times the draws per document must fit the lists");
+  TORCH_CHECK_VALUE(round >= 0, "round must not be negative");
+  const float* w = weight.numel() ? weight.data_ptr<float>() : nullptr;
+  const int ngroups = (int)group_ptr.numel() - 1;
+#define LR_LAUNCH_MEAN(KIND)                                                                  \
+  hipLaunchKernelGGL(lambdarank_mean_tile_kernel<KIND>, dim3((unsigned)T), dim3(LR_BLOCK), 0, \
+                     rank_stream(), margin.data_ptr<float>(), label.data_ptr<float>(), w,     \
+                     group_ptr.data_ptr<int>(), tiles.data_ptr<int>(),                        \
+                     disc_prefix.data_ptr<double>(), (int)n, ngroups, (int)P, (int)flags,     \
+                     (u64)seed, (u64)round, scratch.data_ptr<double>(), gh.data_ptr<float>(), \
+                     pmax.data_ptr<float>())
+  if (kind == LR_NDCG) LR_LAUNCH_MEAN(LR_NDCG);
+  else if (kind == LR_MAP) LR_LAUNCH_MEAN(LR_MAP);
+  else LR_LAUNCH_MEAN(LR_PAIRWISE);
+#undef LR_LAUNCH_MEAN
+  rank_check_launch("lambdarank_mean_tile_kernel");
 }
 
 // One group of rows [gs, gs + m) of the data set, m = order.numel(). s, lab,
@@ -900,6 +1237,10 @@ void init_rank_kernels(pybind11::module_& m) {
   m.def("lambdarank_finish_grid", &lambdarank_finish_grid, "pmax rows of one stream group");
   m.def("lambdarank_tile", &lambdarank_tile,
         "LambdaRank top-k pair gradients of every tile of groups");
+  m.def("lambdarank_mean_list", &lambdarank_mean_list,
+        "draw ids a tile of the sampled (mean) kernel holds: documents times draws");
+  m.def("lambdarank_mean_tile", &lambdarank_mean_tile,
+        "LambdaRank sampled (mean) pair gradients of every tile of groups");
   m.def("lambdarank_stream", &lambdarank_stream,
         "LambdaRank top-k pair gradients of one group larger than a tile");
 }

@@ -364,6 +364,8 @@ def bin_matrix(X, cuts, cut_ptr, stride):
 
 LAMBDARANK_CAP = int(_K.lambdarank_cap())
 LAMBDARANK_FLAG_NORM, LAMBDARANK_FLAG_SCORE, LAMBDARANK_FLAG_EXP_GAIN = 1, 2, 4
+# draw ids one tile of the sampled (mean) kernel holds: documents times draws
+LAMBDARANK_MEAN_LIST = int(_K.lambdarank_mean_list())
 
 
 def _group_tiles(group_ptr, cap, tile_docs, max_groups):
@@ -399,15 +401,21 @@ def _group_tiles(group_ptr, cap, tile_docs, max_groups):
     return ptr, tiles, stream
 
 
-def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None):
-    """Work tables of the top-k LambdaRank gradient (csrc/smxgb_rank.hip)
-    for fixed query groups, built once on the host.
+def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None, pair_method="topk"):
+    """Work tables of the LambdaRank gradients (csrc/smxgb_rank.hip) for
+    fixed query groups, built once on the host.
 
     group_ptr: (G+1,) boundaries rising from 0 to n. Runs of consecutive
     groups become tiles of at most `tile_docs` documents (default and upper
     limit: LAMBDARANK_CAP) and 256 groups; a group larger than
     LAMBDARANK_CAP is served by the stream kernels. The result does not
-    depend on the packing, which is what `tile_docs` is there to show."""
+    depend on the packing, which is what `tile_docs` is there to show.
+
+    pair_method="mean" (lambdarank_mean_gradients): k is the draws per
+    document, and a tile's documents times k must fit the kernel's LDS
+    lists, so `tile_docs` is lowered to LAMBDARANK_MEAN_LIST // k. A group
+    that such a tile cannot hold, one above LAMBDARANK_CAP included, is a
+    ValueError: this path has no stream kernels."""
     cap = LAMBDARANK_CAP
     tile_docs = cap if tile_docs is None else int(tile_docs)
     k = int(k)
@@ -415,11 +423,17 @@ def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None):
         raise ValueError(
             f"lambdarank_num_pair_per_sample must be in [1, {torch_ref.LAMBDARANK_MAX_K}]"
         )
+    if pair_method not in ("topk", "mean"):
+        raise ValueError(f"pair_method must be 'topk' or 'mean', got {pair_method!r}")
+    if pair_method == "mean":
+        tile_docs = min(tile_docs, LAMBDARANK_MEAN_LIST // k)
     ptr, tiles, stream = _group_tiles(group_ptr, cap, tile_docs, int(_K.lambdarank_max_groups()))
+    if pair_method == "mean" and stream:
+        raise ValueError(f"lambdarank_pair_method=mean serves groups of at most {cap} documents")
     n = int(ptr[-1])
     stream = [(gs, m) for _, gs, m in stream]
     dev = torch.device(device)
-    kk = min(k, cap)
+    kk = min(k, cap) if pair_method == "topk" else cap  # mean: IDCG over the whole group
     disc = 1.0 / np.log2(np.arange(kk, dtype=np.float64) + 2.0)
     chunk = int(_K.lambdarank_stream_chunk())
     max_chunks = max([-(-m // chunk) for _, m in stream], default=0)
@@ -427,6 +441,8 @@ def lambdarank_plan(group_ptr, k, device="cuda", tile_docs=None):
     return {
         "n": n,
         "k": k,
+        "pair_method": pair_method,
+        "tile_docs": tile_docs,
         "group_ptr": torch.from_numpy(ptr.astype(np.int32)).to(dev),
         "tiles": torch.tensor(tiles, dtype=torch.int32).reshape(-1, 2).to(dev),
         "n_tiles": len(tiles),
@@ -507,6 +523,36 @@ def lambdarank_gradients(plan, margin, y, weight, kind, flags):
         _K.lambdarank_stream(ss, ll, hits, S, grp, order, w, gs, k, kind, flags, plan["scratch"],
                              plan["part"], plan["psum"], plan["fac"], gh, pmax[rows:rows + step])
         rows += step
+    gh._smxgb_absmax = pmax.amax(dim=0).contiguous()
+    return gh
+
+
+def lambdarank_mean_gradients(plan, margin, y, weight, kind, flags, seed, round):
+    """Sampled (mean) LambdaRank gradients on the device, one kernel launch;
+    the rule and the float64 reference are torch_ref.lambdarank_gradients
+    with pair_method="mean". `plan`: lambdarank_plan(..., pair_method="mean"),
+    whose k is the draws per document. seed, round: what the draws are mixed
+    from, next to the row and the draw's number; round >= 0. Everything
+    else, the `_smxgb_absmax` and its NaN for a NaN margin included, as
+    lambdarank_gradients."""
+    n = plan["n"]
+    if plan["pair_method"] != "mean":
+        raise ValueError("the plan was not built with pair_method='mean'")
+    if not margin.is_cuda or margin.dim() != 1 or margin.numel() != n or y.numel() != n:
+        raise ValueError("margin and y must be 1-d ROCm device tensors with the plan's row count")
+    if int(round) < 0:
+        raise ValueError("round must not be negative")
+    dev = margin.device
+    margin = margin.to(torch.float32).contiguous()
+    y = y.to(torch.float32).contiguous()
+    w = (weight.to(torch.float32).contiguous() if (weight is not None and weight.numel())
+         else torch.empty(0, dtype=torch.float32, device=dev))
+    gh = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    pmax = torch.zeros((plan["n_tiles"], 2), dtype=torch.float32, device=dev)
+    seed = ((int(seed) + 2**63) % 2**64) - 2**63  # any Python int, as the int64 with its bits
+    _K.lambdarank_mean_tile(margin, y, w, plan["group_ptr"], plan["tiles"], plan["disc_prefix"],
+                            plan["k"], plan["tile_docs"], int(kind), int(flags), seed, int(round),
+                            plan["scratch"], gh, pmax)
     gh._smxgb_absmax = pmax.amax(dim=0).contiguous()
     return gh
 

@@ -1163,11 +1163,33 @@ def pred_leaf(flat, X, t_begin=0, t_end=None):
 
 
 # ---------------------------------------------------------------------------
-# LambdaRank top-k pair gradients (lambdarank_pair_method=topk)
+# LambdaRank pair gradients (lambdarank_pair_method=topk and mean)
 # ---------------------------------------------------------------------------
 LAMBDARANK_KINDS = {"rank:pairwise": 0, "rank:ndcg": 1, "rank:map": 2}
 LAMBDARANK_MAX_LABEL = 31
 LAMBDARANK_MAX_K = 4096
+
+
+def lambdarank_mix(seed, round, row, t):
+    """The draw of the sampled (mean) pair method, csrc/smxgb_rank_mix.h in
+    numpy uint64 (arithmetic mod 2^64). With the splitmix64 finaliser
+      fin(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27;
+              z *= 0x94d049bb133111eb; z ^= z >> 31
+    it is fin(fin(seed + 0x9e3779b97f4a7c15 * (round + 1)) ^ ((row << 12) | t)),
+    row < 2^31, t < 4096. `row` may be an array."""
+    import numpy as np
+
+    def fin(z):
+        z = z ^ (z >> np.uint64(30))
+        z = z * np.uint64(0xBF58476D1CE4E5B9)
+        z = z ^ (z >> np.uint64(27))
+        z = z * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+    u = lambda v: np.asarray(v, dtype=np.int64).astype(np.uint64)  # noqa: E731
+    with np.errstate(over="ignore"):
+        key = fin(u([seed]) + np.uint64(0x9E3779B97F4A7C15) * (u([round]) + np.uint64(1)))
+        return fin(key ^ ((u(row) << np.uint64(12)) | np.uint64(t)))
 
 
 def check_lambdarank_labels(y, kind):
@@ -1189,8 +1211,9 @@ def check_lambdarank_labels(y, kind):
 
 def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg", k=32,
                          normalization=True, score_normalization=True, exp_gain=True,
-                         details=False):
-    """LambdaRank gradients with the top-k pair method, in float64.
+                         details=False, pair_method="topk", seed=0, round=0):
+    """LambdaRank gradients with the top-k or the sampled (mean) pair method,
+    in float64.
 
     This function IS the definition of the rule here. It is modelled on the
     published description of upstream XGBoost 3.x's LambdaGrad with
@@ -1222,6 +1245,16 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
     h(p) and S(p) = sum over relevant q <= p of 1 / (q + 1):
       positions u < v, u relevant:  R dAP = h(v)/(v+1) - h(u)/(u+1) - (S(v) - S(u))
                        v relevant:  R dAP = (h(u)+1)/(u+1) - (h(v)+1)/(v+1) + (S(v) - S(u)).
+
+    pair_method="mean" changes the pairs and nothing else. `k` is then P,
+    the draws per document. The document at local index a (its row minus
+    the group's first row) of a group of m >= 2 draws, for t = 0 .. P-1,
+      r = lambdarank_mix(seed, round, row, t);
+      b = ((r >> 32) * (m - 1)) >> 32;  b += (b >= a)
+    (integers only) and the pair (a, b) is kept iff the labels differ. The
+    pairs are a multiset: one drawn twice, or from both ends, counts each
+    time. The pair set depends on (seed, round, row, t, m) alone, never on
+    the margins. The IDCG of rank:ndcg runs over the whole group.
 
     Returns the packed (n, 2) float32 [g, h] on margin's device; with
     `details` a dict of float64 numpy arrays instead: g, h, and mass =
@@ -1255,6 +1288,8 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
     a_out = np.zeros(n)
     gain_of = (2.0 ** np.arange(LAMBDARANK_MAX_LABEL + 1) - 1.0) if exp_gain else np.arange(
         LAMBDARANK_MAX_LABEL + 1, dtype=np.float64)
+    if pair_method not in ("topk", "mean"):
+        raise ValueError(f"pair_method must be 'topk' or 'mean', got {pair_method!r}")
     block = 1 << 16  # columns of the (top-k x group) pair matrix held at once
     for g0, g1 in zip(ptr[:-1], ptr[1:]):
         m = int(g1 - g0)
@@ -1265,7 +1300,7 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
         ll = lab_all[g0:g1][order]
         if ll.min() == ll.max():
             continue
-        K = min(k, m)
+        K = min(k, m) if pair_method == "topk" else m
         pos = np.arange(m, dtype=np.float64)
         if kind == "rank:ndcg":
             gains = gain_of[ll]
@@ -1278,10 +1313,10 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
         gs = np.zeros(m)
         hs = np.zeros(m)
         sig = 0.0
-        R = np.arange(K)[:, None]
-        for c0 in range(0, m, block):
-            Q = np.arange(c0, min(c0 + block, m))[None, :]
-            valid = (Q > R) & (ll[R] != ll[Q])
+
+        def terms(R, Q, valid):
+            """lambda, eta and the lambda the document at position R receives,
+            of the pairs of positions (R, Q); zero where not `valid`."""
             r_hi = ll[R] > ll[Q]
             d = np.where(r_hi, ss[R] - ss[Q], ss[Q] - ss[R])
             if kind == "rank:pairwise":
@@ -1290,11 +1325,11 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
                 delta = (np.abs((gains[R] - gains[Q]) * (disc[R] - disc[Q])) / idcg
                          if idcg > 0.0 else np.zeros_like(d))
             else:
-                u_rel = ll[R] > 0  # R < Q wherever the pair is valid
+                U, V = np.minimum(R, Q), np.maximum(R, Q)
                 dap = np.where(
-                    u_rel,
-                    hits[Q] / (Q + 1.0) - hits[R] / (R + 1.0) - (S[Q] - S[R]),
-                    (hits[R] + 1.0) / (R + 1.0) - (hits[Q] + 1.0) / (Q + 1.0) + (S[Q] - S[R]),
+                    ll[U] > 0,
+                    hits[V] / (V + 1.0) - hits[U] / (U + 1.0) - (S[V] - S[U]),
+                    (hits[U] + 1.0) / (U + 1.0) - (hits[V] + 1.0) / (V + 1.0) + (S[V] - S[U]),
                 )
                 delta = np.abs(dap) / hits[-1]
             with np.errstate(over="ignore"):
@@ -1303,7 +1338,27 @@ def lambdarank_gradients(margin, y, group_ptr=None, weight=None, kind="rank:ndcg
                 delta = delta / (np.abs(d) + 0.01)
             lam = np.where(valid, rho * delta, 0.0)
             eta = np.where(valid, np.maximum(rho * (1.0 - rho), 1e-16) * delta * 2.0, 0.0)
-            signed = np.where(r_hi, -lam, lam)  # what the document at r receives
+            return lam, eta, np.where(r_hi, -lam, lam)
+
+        if pair_method == "mean":
+            rank = np.empty(m, dtype=np.int64)
+            rank[order] = np.arange(m)
+            a = np.arange(m, dtype=np.int64)
+            for t in range(k):
+                r = lambdarank_mix(seed, round, g0 + a, t)
+                b = (((r >> np.uint64(32)) * np.uint64(m - 1)) >> np.uint64(32)).astype(np.int64)
+                b += b >= a
+                R, Q = rank, rank[b]  # positions of the drawers and of their partners
+                lam, eta, signed = terms(R, Q, ll[R] != ll[Q])
+                for at, sign in ((R, 1.0), (Q, -1.0)):
+                    np.add.at(gs, at, sign * signed)
+                    np.add.at(hs, at, eta)
+                    np.add.at(a_out, g0 + order[at], lam)
+                sig += 2.0 * float(lam.sum())
+        R = np.arange(K if pair_method == "topk" else 0)[:, None]
+        for c0 in range(0, m if pair_method == "topk" else 0, block):
+            Q = np.arange(c0, min(c0 + block, m))[None, :]
+            lam, eta, signed = terms(R, Q, (Q > R) & (ll[R] != ll[Q]))
             gs[:K] += signed.sum(axis=1)
             gs[Q[0]] -= signed.sum(axis=0)
             hs[:K] += eta.sum(axis=1)

@@ -59,6 +59,7 @@ setup(
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_cat.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_jobs.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize.h",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_rank_mix.h",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_shap.h",
             ],
             extra_compile_args={
