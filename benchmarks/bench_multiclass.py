@@ -42,6 +42,8 @@ def main():
     ap.add_argument("--rows", type=int, default=581_012)
     ap.add_argument("--features", type=int, default=54)
     ap.add_argument("--classes", type=int, default=7)
+    ap.add_argument("--eval", action="store_true",
+                    help="also report mlogloss and merror of the training set every round")
     args = ap.parse_args()
 
     use_gpu = torch.cuda.is_available()
@@ -66,9 +68,11 @@ def main():
             "tree_method": "gpu_hist" if use_gpu else "hist",
             "max_depth": 6,
             "device": str(device),
+            "eval_metric": ["mlogloss", "merror"],
         },
         dtrain,
         num_boost_round=args.warmup + args.steps,
+        evals=[(dtrain, "train")] if args.eval else (),
         callbacks=[timer],
         verbose_eval=False,
     )
@@ -82,6 +86,8 @@ def main():
                 "rows": rows,
                 "features": args.features,
                 "num_class": args.classes,
+                "eval": args.eval,
+                "softmax": os.environ.get("SMXGB_SOFTMAX", "hip"),
                 "device": str(device),
             }
         )

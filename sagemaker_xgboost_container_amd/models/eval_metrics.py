@@ -2,8 +2,9 @@
 
 Computed with torch on whatever device the margins live on (GPU during
 training: predictions never leave HBM). AUC uses a sort-based exact
-computation; on a ROCm device, binary auc and ndcg / map run HIP kernels
-instead (ops/hip.binary_auc, ops/hip.rank_metric). Names/directions match
+computation; on a ROCm device, binary auc, ndcg / map and mlogloss / merror
+run HIP kernels instead (ops/hip.binary_auc, ops/hip.rank_metric,
+ops/hip.softmax_metric). Names/directions match
 constants/xgb_constants.py.
 """
 import math
@@ -310,6 +311,19 @@ def _device_auc(margin, y, weight, plans):
     return hip.binary_auc(plan, margin)
 
 
+def _device_softmax_metric(name, margin, y, weight):
+    """mlogloss / merror through the HIP kernel (ops/hip.softmax_metric): the
+    weighted sum of the rows' terms over the weight sum, two float64 values
+    read back at once, no softmax tensor. None where the kernel does not
+    serve the call (more classes than its cap, SMXGB_SOFTMAX=torch)."""
+    from ..ops import hip
+
+    sums = hip.softmax_metric(name, margin, y, weight)
+    if sums is None:
+        return None
+    return sums[0] / sums[1] if sums[1] else float("nan")
+
+
 def evaluate(metric_name, margin, y, weight, objective, group_ptr=None, rank_plans=None):
     """Compute one named metric from raw margins via the objective transform.
 
@@ -336,6 +350,11 @@ def evaluate(metric_name, margin, y, weight, objective, group_ptr=None, rank_pla
     elif name in ("auc", "aucpr"):
         pred = margin  # rank-based: margin ordering == prob ordering
     elif name in ("merror", "mlogloss"):
+        if (margin.is_cuda and margin.dim() == 2 and margin.numel() and y.numel() == margin.shape[0]
+                and os.environ.get("SMXGB_FORCE_TORCH_OPS") != "1"):
+            value = _device_softmax_metric(name, margin, y, weight)
+            if value is not None:
+                return value
         pred = torch.softmax(margin, dim=-1)
     elif name in ("poisson-nloglik", "gamma-nloglik", "gamma-deviance", "tweedie-nloglik"):
         pred = torch.exp(margin)

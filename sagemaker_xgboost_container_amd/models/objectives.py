@@ -340,6 +340,7 @@ class Softmax(Objective):
         if self.num_class < 2:
             raise ValueError("num_class must be >= 2 for multi-class objectives")
         self.n_outputs = self.num_class
+        self._cap_logged = False
 
     def validate_labels(self, y):
         if bool(((y < 0) | (y >= self.num_class)).any()):
@@ -352,7 +353,19 @@ class Softmax(Objective):
         return torch.softmax(margin, dim=-1)
 
     def gradients(self, margin, y, weight=None):
-        # margin: (n, k); returns (n, k, 2)
+        # margin: (n, k); returns (n, k, 2). On a ROCm device one kernel
+        # (ops/hip.softmax_gradients) writes it class-major, with the
+        # per-class absmax; above its class cap the torch code below runs.
+        if margin.is_cuda and os.environ.get("SMXGB_FORCE_TORCH_OPS") != "1":
+            from ..ops import hip as _hip  # raises if the extension is missing on GPU
+
+            gh = _hip.softmax_gradients(margin, y, weight)
+            if gh is not None:
+                return gh
+            if self.num_class > _hip.SOFTMAX_CAP and not self._cap_logged:
+                self._cap_logged = True
+                logger.debug("%s: num_class=%d is above the softmax kernel's %d, torch gradients",
+                             self.name, self.num_class, _hip.SOFTMAX_CAP)
         p = torch.softmax(margin, dim=-1)
         onehot = torch.nn.functional.one_hot(y.long(), self.num_class).to(p.dtype)
         g = p - onehot

@@ -140,6 +140,20 @@ def _csr_tree_margin_fn(csr, device):
     return lambda tree: predict_tree_csr(tree, csr)
 
 
+def _class_gradients(gh, cls):
+    """The contiguous (n, 2) gradients of one class of a (n, k, 2) tensor.
+    ops/hip.softmax_gradients hands out a view of a class-major buffer with
+    the per-class absmax of the same pass: the slice is then no copy, and
+    carries its absmax so that compute_scale does not reduce it again. It
+    gets no `_smxgb_rootsum`: the per-level grower keeps its own root sum."""
+    absmax = getattr(gh, "_smxgb_class_absmax", None)
+    if absmax is None:
+        return gh[:, cls, :].contiguous()
+    gh_cls = gh[:, cls, :]
+    gh_cls._smxgb_absmax = absmax[cls]
+    return gh_cls
+
+
 class _AdaptiveLeaves:
     """Adaptive tree leaves (reg:absoluteerror, reg:quantileerror): once a
     tree's structure is grown, every leaf value becomes eta times the
@@ -570,7 +584,7 @@ def train(
 
         if booster_kind == "gblinear":
             for cls in range(n_outputs):
-                gh_cls = gh if n_outputs == 1 else gh[:, cls, :].contiguous()
+                gh_cls = gh if n_outputs == 1 else _class_gradients(gh, cls)
                 delta = linear_updater.update_round(booster.linear_model, X, gh_cls, cls)
                 margin[:, cls] += delta
             booster.add_iteration([], [])
@@ -615,7 +629,7 @@ def train(
             for _parallel in range(num_parallel_tree):
                 if pipeline_classes:
                     handles = [
-                        grower.grow_async(gh[:, cls, :].contiguous(), slot=cls)
+                        grower.grow_async(_class_gradients(gh, cls), slot=cls)
                         for cls in range(n_outputs)
                     ]
                     for cls, handle in enumerate(handles):
@@ -630,7 +644,7 @@ def train(
                                 es.margin[:, cls] += es.tree_margin(backend, tree)
                     continue
                 for cls in range(n_outputs):
-                    gh_cls = gh if n_outputs == 1 else gh[:, cls, :].contiguous()
+                    gh_cls = gh if n_outputs == 1 else _class_gradients(gh, cls)
                     tree, leaf_jobs = grower.grow(gh_cls)
                     if adaptive is not None:
                         leaf_jobs = adaptive.update(tree, leaf_jobs, grower, round_margin[:, cls], cls)

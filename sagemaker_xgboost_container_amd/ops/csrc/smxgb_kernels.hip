@@ -3462,6 +3462,7 @@ void init_rank_metric_kernels(pybind11::module_& m);
 void init_quantize_kernels(pybind11::module_& m);
 void init_quantize_csr_kernels(pybind11::module_& m);
 void init_auc_kernels(pybind11::module_& m);
+void init_multiclass_kernels(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_text_parsers(m);
@@ -3474,6 +3475,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   init_quantize_kernels(m);
   init_quantize_csr_kernels(m);
   init_auc_kernels(m);
+  init_multiclass_kernels(m);
   m.def("hist_build", &hist_build, "batched LDS-staged fixed-point histogram build");
   m.def("hist_convert", &hist_convert, "fixed-point -> float32 histogram convert");
   m.def("partition", &partition, "batched two-ended row partition");

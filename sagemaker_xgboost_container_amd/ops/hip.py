@@ -737,6 +737,114 @@ def binary_auc(plan, margin):
     return float(out)
 
 
+# Multiclass objective and metrics (csrc/smxgb_multiclass.hip). "hip" (the
+# default) runs softmax_grad_kernel / softmax_metric_kernel for
+# multi:softprob / multi:softmax and mlogloss / merror on a ROCm device,
+# "torch" keeps the torch code of models/objectives.Softmax.gradients and
+# models/eval_metrics for A/B runs; SMXGB_FORCE_TORCH_OPS=1 wins over it.
+# Read once at import; set_softmax_mode() switches it within a process.
+_SOFTMAX = _os.environ.get("SMXGB_SOFTMAX", "hip")
+_SOFTMAX_MODES = ("hip", "torch")
+
+
+def set_softmax_mode(mode):
+    """Select how multiclass gradients and metrics are computed from now on
+    ("hip" or "torch"); returns the mode that was set before."""
+    global _SOFTMAX
+    if mode not in _SOFTMAX_MODES:
+        raise ValueError(f"SMXGB_SOFTMAX must be one of {list(_SOFTMAX_MODES)}, got {mode!r}")
+    previous = _SOFTMAX
+    _SOFTMAX = mode
+    return previous
+
+
+def softmax_mode():
+    from . import _FORCE_TORCH
+
+    return "torch" if _FORCE_TORCH else _SOFTMAX
+
+
+set_softmax_mode(_SOFTMAX)
+
+_SOFTMAX_GRID = int(_K.softmax_max_grid())
+SOFTMAX_METRIC_KINDS = {"mlogloss": 0, "merror": 1}
+
+
+def softmax_tile_rows(k):
+    """Rows of margin a workgroup of the softmax kernels keeps in LDS at a
+    time for k classes: the most, up to 512 in steps of 64, that fit the LDS
+    budget at 4 * (k | 1) + 12 bytes a row; 0 where 64 rows do not fit."""
+    return int(_K.softmax_tile_rows(int(k), _LDS_BYTES))
+
+
+# the most classes the softmax kernels serve: 64 rows still fit the budget
+# (213 at the default 56 KiB); a larger num_class keeps the torch code
+SOFTMAX_CAP = next(k - 1 for k in range(2, 1 << 14) if softmax_tile_rows(k) == 0)
+
+
+def _softmax_launch_shape(margin, y, weight):
+    """(tile rows, grid, y, weight) of a softmax kernel launch, or None where
+    the kernels do not serve the call."""
+    if (softmax_mode() != "hip" or not margin.is_cuda or margin.dim() != 2
+            or margin.dtype != torch.float32 or y.device != margin.device
+            or y.numel() != margin.shape[0]
+            or not (1 <= margin.shape[0] < 2**31) or not (2 <= margin.shape[1] <= SOFTMAX_CAP)):
+        return None
+    rows = softmax_tile_rows(margin.shape[1])
+    if rows == 0:
+        return None
+    weighted = weight is not None and weight.numel() > 0
+    if weighted and (weight.device != margin.device or weight.numel() != y.numel()):
+        return None
+    w = (weight.to(torch.float32).contiguous() if weighted
+         else torch.empty(0, dtype=torch.float32, device=margin.device))
+    grid = min(-(-margin.shape[0] // rows), _SOFTMAX_GRID)
+    return rows, grid, y.to(torch.float32).contiguous(), w
+
+
+def softmax_gradients(margin, y, weight=None):
+    """Multiclass gradients in one pass (softmax_grad_kernel); the rule is
+    models/objectives.Softmax.gradients, p in float32 by torch.softmax's
+    steps. margin: (n, k) float32 on a ROCm device, y: (n,) class ids.
+
+    Returns the (n, k, 2) view of a class-major (k, n, 2) buffer, so that
+    gh[:, c, :] is contiguous, with `_smxgb_class_absmax` attached: (k, 2),
+    abs().amax(0) of every class's slice, from the same pass. Nothing is
+    read back and the result is the same bit for bit from call to call.
+    Returns None when it does not serve the call (caller falls back to the
+    torch path): not on the device, not float32, more than SOFTMAX_CAP
+    classes, or switched off (SMXGB_SOFTMAX=torch, SMXGB_FORCE_TORCH_OPS=1)."""
+    shape = _softmax_launch_shape(margin, y, weight)
+    if shape is None:
+        return None
+    rows, grid, y, w = shape
+    n, k = margin.shape
+    buf = torch.empty((k, n, 2), dtype=torch.float32, device=margin.device)
+    pmax = torch.empty((grid, k, 2), dtype=torch.float32, device=margin.device)
+    _K.softmax_grad(margin.contiguous(), y, w, buf, pmax, rows)
+    gh = buf.permute(1, 0, 2)
+    gh._smxgb_class_absmax = pmax.amax(dim=0).contiguous()
+    return gh
+
+
+def softmax_metric(kind, margin, y, weight=None):
+    """(numerator, denominator) of "mlogloss" or "merror" for (n, k) margins
+    on a ROCm device: the float64 sums of w * term and of w over the rows
+    (softmax_metric_kernel), the one readback of the call. The softmax is
+    never formed: the mlogloss term is min(logsumexp - m_y, -log(1e-16)) in
+    float64, the merror term argmax != y with the lowest class among equal
+    margins as the argmax. Returns None under softmax_gradients' conditions."""
+    shape = _softmax_launch_shape(margin, y, weight)
+    if shape is None:
+        return None
+    rows, grid, y, w = shape
+    part = torch.empty((grid, 2), dtype=torch.float64, device=margin.device)
+    out = torch.empty(2, dtype=torch.float64, device=margin.device)
+    _K.softmax_metric(margin.contiguous(), y, w, part, out, rows, SOFTMAX_METRIC_KINDS[kind])
+    num, den = out.tolist()
+    return num, den
+
+
 # Supported max_bin range of this backend, stated once. The split search
 # takes any number of bins (features above SPLIT_SCAN_BINS real bins go
 # through the wide split scan). The histogram kernels keep one feature's

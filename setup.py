@@ -52,6 +52,7 @@ setup(
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_quantize_csr.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/smxgb_auc.hip",
+                "sagemaker_xgboost_container_amd/ops/csrc/smxgb_multiclass.hip",
                 "sagemaker_xgboost_container_amd/ops/csrc/text_parsers.cpp",
             ],
             # headers shared by the sources: a change rebuilds the extension
